@@ -20,6 +20,11 @@ datasets/__init__.py:37-38 of the reference); without it every rank renders one 
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (sdf_mlp) timed with HIP events on the launch
 stream inside the timed region; `roofline_kernels` lists the other contraction kernels; `cpu_baseline` is the CPU
 oracle (oracle/surf_oracle.py, a port of the reference algorithm) timed on this host on a bounded ray subset.
+A plain run sets up, warms up, times the steps and prints the line; everything measured beyond the headline (the CPU
+baselines, the other precisions and BASELINE configurations, the volume build, scene and training-step timings, the mesh
+lattice, the collective probe, the training line's per-kernel pass) runs only with `--full` (see FULL_ONLY; an option
+given explicitly still counts).  `--dump-outputs DIR` writes what the timed path computed in its last step as
+DIR/<name>.npy (dump_outputs); the inputs are seeded, so two builds run with the same arguments compare output for output.
 `--workload train` (configs[3]) instead runs the data-parallel TRAINING step: every rank one scene + 512 rays per step
 through the reference's own sequence (forward, Loss, loss.backward(), Adam) with the model wrapped in
 DistributedDataParallel over RCCL; it reports training rays/s, steps/s, the all-reduce time of the gradient bucket alone
@@ -72,6 +77,40 @@ WORKLOADS = {
               "metric": "training rays/sec (surf.conf unsupervised training step, 5 views 576x800, 128 samp/ray, whole job)"},
 }
 RAY_CHUNK = 1 << 19      # rays per render call (bounds the per-sample buffers; 576x800 fits one call)
+# options whose default is (with --full, without): a plain run measures the headline alone
+FULL_ONLY = {"cpu_seconds": (10.0, 0.0), "build": (1, 0), "train_step": (1, 0), "mesh_grid": (512, 0), "also": ("f16x2", ""),
+             "other_configs": (1, 0), "kernel_pass": (1, 0)}
+DUMP_BYTES = 60_000_000  # --dump-outputs: total size cap of the written arrays (64 MB with headroom for the .npy headers)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write every tensor of `arrays` (name -> tensor) as path/<name>.npy, float64 tensors and integer
+    tensors as float64, everything else as float32.  DUMP_BYTES is shared out smallest array first, so that the small ones
+    are written whole; an array larger than its share is written as a fixed sample of its rows (seed 0, ascending row
+    order, the same rows for every array of that row count), or of its elements when a single row exceeds the share.
+    Returns {name: written shape}."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    conv = {}
+    for name, t in arrays.items():
+        if torch.is_tensor(t):
+            t = t.detach()
+            wide = t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool or t.dtype == torch.uint8)
+            conv[name] = t.cpu().double() if wide else t.cpu().float()
+    left, written = DUMP_BYTES, {}
+    for i, (name, t) in enumerate(sorted(conv.items(), key=lambda kv: (kv[1].numel() * kv[1].element_size(), kv[0]))):
+        share = left // (len(conv) - i)
+        if t.numel() * t.element_size() > share:
+            rows = t.reshape(t.shape[0], -1) if t.dim() > 1 else t.reshape(-1, 1)
+            if rows.shape[1] * t.element_size() > share:
+                rows = t.reshape(-1, 1)
+            n = max(1, share // (rows.shape[1] * t.element_size()))
+            idx = torch.randperm(rows.shape[0], generator=torch.Generator().manual_seed(0))[:n].sort().values
+            t = rows[idx].reshape((n,) + tuple(t.shape[1:])) if rows.shape[0] == t.shape[0] else rows[idx].reshape(-1)
+        np.save(os.path.join(path, f"{name}.npy"), t.numpy())
+        left -= t.numel() * t.element_size()
+        written[name] = list(t.shape)
+    return dict(sorted(written.items()))
 
 
 def model_conf(n_samples, sdf_precision="bf16x3", blend_precision=None):
@@ -641,6 +680,10 @@ def run_rank_train(args):
     D.barrier()
     sync()
     elapsed = D.max_over_ranks(time.perf_counter() - t0, dev)
+    dumped = None
+    if args.dump_outputs and rank == 0 and not dry:
+        # what a caller of the training step receives: its loss and the parameters the optimiser step wrote
+        dumped = dump_outputs(args.dump_outputs, {"loss": loss, **{"param." + n: p for n, p in model.named_parameters()}})
     events = []
     if not dry and args.kernel_pass:
         # per-kernel rooflines: the same K steps again, OUTSIDE the timed region, with a HIP event pair around each instrumented
@@ -654,7 +697,7 @@ def run_rank_train(args):
     # the gradient all-reduce alone: one flat bucket of the trainable parameters' size (DDP's single 5.6 MB bucket)
     n_params = sum(p.numel() for p in model.parameters() if p.requires_grad)
     allreduce_ms = None
-    if grouped:
+    if grouped and args.full:
         flat = torch.zeros(n_params, dtype=torch.float32, device=dev)
         for _ in range(3):
             torch.distributed.all_reduce(flat)
@@ -698,6 +741,8 @@ def run_rank_train(args):
             result["cpu_baseline"] = cpu_train_baseline()
         if not dry:
             result["voxels_per_stage"] = getattr(model, "last_voxels_per_stage", None)
+        if dumped is not None:
+            result["dumped_outputs"] = dumped
         result["collective_backend"] = collective_note(args)
         return result
     return None
@@ -778,23 +823,30 @@ def parse_args(argv):
     ap.add_argument("--width", type=int, default=None)
     ap.add_argument("--views", type=int, default=None)
     ap.add_argument("--n-samples", type=str, default=None)
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="time budget of the CPU baseline (0 = skip)")
-    ap.add_argument("--build", type=int, default=1, help="also time one full volume build (FPN + 4 stages), N=1 only")
-    ap.add_argument("--train-step", type=int, default=1, help="also time one full training step (N=1, dtu workload)")
-    ap.add_argument("--mesh-grid", type=int, default=512, help="also time the resolution^3 SDF lattice of "
-                                                               "extract_geometry (0 = skip), N=1 only")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline (CPU baselines, other precisions and configurations, "
+                         "volume build, scene, training step, mesh lattice, collective probe, the training line's kernel pass): "
+                         "the defaults of the options below that are marked [--full]")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all: larger arrays as a fixed, seeded sample of their rows)")
+    ap.add_argument("--cpu-seconds", type=float, default=None, help="time budget of the CPU baseline (0 = skip) [--full: 10]")
+    ap.add_argument("--build", type=int, default=None, help="also time one full volume build (FPN + 4 stages), N=1 only [--full: 1]")
+    ap.add_argument("--train-step", type=int, default=None, help="also time one full training step (N=1, dtu workload) [--full: 1]")
+    ap.add_argument("--mesh-grid", type=int, default=None, help="also time the resolution^3 SDF lattice of "
+                                                                "extract_geometry (0 = skip), N=1 only [--full: 512]")
     ap.add_argument("--sdf-precision", default="bf16x3", choices=sorted(SDF_KERNELS),
                     help="SDF kernel: f32 MFMA, bf16x3 (exact 3-way bf16 split, fp32-equivalent; default), "
                          "f16x2 (22-bit operands, fastest)")
     ap.add_argument("--blend-precision", default=None, choices=sorted(BLEND_KERNELS),
                     help="blending kernel (default: the library's default, see surf_amd.ops.BLEND_DEFAULT)")
-    ap.add_argument("--also", default="f16x2", help="comma list of further precisions timed after the headline run "
-                                                    "(reported under other_precisions; '' = none)")
+    ap.add_argument("--also", default=None, help="comma list of further precisions timed after the headline run "
+                                                 "(reported under other_precisions; '' = none) [--full: f16x2]")
     ap.add_argument("--dry", action="store_true", help="control-flow test: no GPU, no kernels, gloo instead of RCCL")
     ap.add_argument("--rank-timeout", type=float, default=1700.0, help="self-spawned ranks are killed after this many seconds")
-    ap.add_argument("--kernel-pass", type=int, default=1, help="--workload train: after the timed steps, the same steps again "
+    ap.add_argument("--kernel-pass", type=int, default=None, help="--workload train: after the timed steps, the same steps again "
                     "with a HIP event pair around every instrumented launch (in-order launches) for the per-kernel rooflines; "
-                    "0 under rocprofv3, whose trace then holds exactly warmup + steps training steps")
+                    "0 under rocprofv3, whose trace then holds exactly warmup + steps training steps [--full: 1]")
     ap.add_argument("--rays", type=int, default=512, help="--workload train: rays per rank and step (confs/surf.conf: 512)")
     ap.add_argument("--train-precision", default="fp32", choices=["fp32", "bf16"],
                     help="training-backward policy (model conf key train_precision): bf16 = weight-gradient reductions on bf16 operands")
@@ -810,9 +862,9 @@ def parse_args(argv):
                          "the N-rank runs (barrier, device-tensor MAX, record gather, gather_rows, gradient bucket, DDP) executes over "
                          "RCCL on a one-GPU box; 0 = no group at N = 1")
     ap.add_argument("--group-timeout", type=float, default=600.0, help="process-group timeout in seconds")
-    ap.add_argument("--other-configs", type=int, default=1,
+    ap.add_argument("--other-configs", type=int, default=None,
                     help="default N = 1 dtu line: also measure configs[4] (T&T shape), configs[2] (15 scenes on this GPU) and the "
-                         "single-scene ray split, reported under other_configs")
+                         "single-scene ray split, reported under other_configs [--full: 1]")
     ap.add_argument("--fail-rank", type=int, default=-1, help="(tests) this rank exits 3 before the first barrier")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend of a multi-rank run: nccl (= RCCL, the measured configuration) or gloo (tests: "
@@ -827,6 +879,9 @@ def parse_args(argv):
     for k in ("height", "width", "views", "n_samples"):
         if getattr(args, k) is None:
             setattr(args, k, wl[k])
+    for k, (full, plain) in FULL_ONLY.items():
+        if getattr(args, k) is None:
+            setattr(args, k, full if args.full else plain)
     return args
 
 
@@ -914,6 +969,7 @@ def run_rank_split(args):
     D.barrier()
     torch.cuda.synchronize()
     elapsed = D.max_over_ranks(time.perf_counter() - t0, dev)
+    dumped = dump_outputs(args.dump_outputs, {"color_fine": image}) if args.dump_outputs and rank == 0 else None
     # the rank's own share of the time: render alone (HIP events) vs render + gather
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
@@ -963,7 +1019,7 @@ def run_rank_split(args):
                        "rays_per_rank": [(k + 1) * R // world - k * R // world for k in range(world)]},
             "split": {"render_ms_max_over_ranks": render_ms, "step_ms": elapsed / args.steps * 1e3, "lattice": lattice, "check": check},
             "roofline": None, "cpu_baseline": None,
-            "collective_backend": collective_note(args)})
+            "collective_backend": collective_note(args)} | ({"dumped_outputs": dumped} if dumped is not None else {}))
     return None
 
 
@@ -1078,6 +1134,9 @@ def run_rank(args):
         events, model.kernel_events = model.kernel_events, None
         active_log, model.active_samples_log = model.active_samples_log, None
     elapsed = D.max_over_ranks(elapsed, dev)
+    dumped = None
+    if args.dump_outputs and rank == 0 and not dry:
+        dumped = dump_outputs(args.dump_outputs, out)      # the render output of the last scene of the last timed step
 
     # ---- per-scene records (gathered: one small object per rank, no tensor traffic) ------------------------
     my_rec = []
@@ -1135,7 +1194,7 @@ def run_rank(args):
         model.blend_precision = blend_precision
 
     # the timed collectives of the group (EVERY rank takes part: all-reduce of the gradient bucket, gather_rows, barrier)
-    probe = collective_probe(dev)
+    probe = collective_probe(dev) if args.full else None
     if rank == 0:
         sdf_kernel, sdf_pipe, pipe_peak, n_prod = SDF_KERNELS[args.sdf_precision]
         sdf_ms = kernel_ms["sdf_mlp"]
@@ -1198,6 +1257,8 @@ def run_rank(args):
             result["scenes"] = recs
         if others:
             result["other_precisions"] = others
+        if dumped is not None:
+            result["dumped_outputs"] = dumped
         sc0 = scenes[0]
         if world == 1 and args.mesh_grid > 0:
             total_ms, k_ms, inside, mc = mesh_grid_timing(model, sc0["scene"], dev, args.mesh_grid)
@@ -1259,7 +1320,7 @@ def other_configs(args):
     jobs = [("tnt", ["--workload", "tnt", "--steps", "3", "--warmup", "1"]),
             ("scenes15", ["--scenes", "15", "--steps", "1", "--warmup", "1"]),
             ("split_rays", ["--split", "rays", "--check-split", "--steps", "3", "--warmup", "1", "--mesh-grid", "512"])]
-    common = ["--gpus", "1", "--cpu-seconds", "0", "--build", "0", "--train-step", "0", "--also", "", "--other-configs", "0",
+    common = ["--full", "--gpus", "1", "--cpu-seconds", "0", "--build", "0", "--train-step", "0", "--also", "", "--other-configs", "0",
               "--sdf-precision", args.sdf_precision, "--base-dim", str(args.base_dim)]
     res = {}
     for name, argv in jobs:

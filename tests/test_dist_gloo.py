@@ -186,7 +186,7 @@ def test_bench_train_workload_two_ranks_ddp_dry():
     DistributedDataParallel (gloo here, RCCL on GPUs), the runner's step sequence, one line with training rays/s, steps/s
     and the all-reduce time of the gradient bucket."""
     import json
-    res = subprocess.run([sys.executable, BENCH, "--workload", "train", "--gpus", "2", "--dry", "--steps", "3", "--warmup", "1"],
+    res = subprocess.run([sys.executable, BENCH, "--workload", "train", "--full", "--gpus", "2", "--dry", "--steps", "3", "--warmup", "1"],
                          env=_clean_env(), capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.strip().splitlines() if l.startswith("{")]

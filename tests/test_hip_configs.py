@@ -78,7 +78,7 @@ def test_bench_train_workload_line_on_one_gpu():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "train", "--steps", "2", "--warmup", "1", "--height", "96",
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "train", "--full", "--steps", "2", "--warmup", "1", "--height", "96",
                           "--width", "128", "--base-dim", "16", "--rays", "128"], env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.strip().splitlines() if ln.startswith("{")]
@@ -138,7 +138,7 @@ def test_bench_two_ranks_share_the_gpu_render():
 def test_bench_two_ranks_share_the_gpu_train():
     """BASELINE configs[3]'s N > 1 leg with its real kernels: two ranks on cuda:0, DistributedDataParallel over gloo (bucket hooks,
     the broadcast at wrap time, the gradient all-reduce timing) - what RCCL serves on an 8-GPU node."""
-    r = _bench(["--workload", "train", "--gpus", "2", "--backend", "gloo", "--one-gpu", "--steps", "2", "--warmup", "1", "--height", "96",
+    r = _bench(["--workload", "train", "--full", "--gpus", "2", "--backend", "gloo", "--one-gpu", "--steps", "2", "--warmup", "1", "--height", "96",
                 "--width", "128", "--base-dim", "16", "--rays", "128"])
     assert r["n_gpus"] == 2 and r["config"]["parallelism"] == "ddp2" and r["config"]["rays_per_rank_step"] == 128
     assert r["gradient_allreduce_ms"] > 0 and r["loss"] == r["loss"] and r["collective_backend"].startswith("gloo")

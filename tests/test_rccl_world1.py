@@ -209,12 +209,12 @@ SMALL = ["--steps", "2", "--warmup", "1", "--height", "48", "--width", "64", "--
 
 def test_bench_default_group_is_world1_rccl():
     """`bench.py --gpus 1` forces the world-1 RCCL group by default: the line names it and carries the timed collectives."""
-    r = _bench(["--gpus", "1"] + SMALL)
+    r = _bench(["--gpus", "1", "--full"] + SMALL)
     assert r["collective_backend"].startswith("nccl") and "world 1" in r["collective_backend"]
     c = r["collectives"]
     assert c["world"] == 1 and c["backend"] == "nccl" and c["bucket_bytes"] == 5_640_000
     assert c["allreduce_identity_at_world_1"] and c["gather_rows_identity_at_world_1"] and c["gradient_bucket_allreduce_ms"] > 0
-    r0 = _bench(["--gpus", "1", "--force-group", "0"] + SMALL)
+    r0 = _bench(["--gpus", "1", "--force-group", "0", "--full"] + SMALL)
     assert r0["collective_backend"] is None and r0["collectives"] is None
 
 
@@ -222,7 +222,7 @@ def test_bench_split_and_train_over_world1_rccl():
     r = _bench(["--split", "rays", "--check-split", "--gpus", "1", "--steps", "1", "--warmup", "1", "--height", "48", "--width", "64",
                 "--base-dim", "16", "--mesh-grid", "32"])
     assert r["collective_backend"].startswith("nccl") and r["split"]["check"] == {"image_bit_equal": True, "lattice_bit_equal": True}
-    t = _bench(["--workload", "train", "--steps", "2", "--warmup", "1", "--height", "96", "--width", "128", "--base-dim", "16",
+    t = _bench(["--workload", "train", "--full", "--steps", "2", "--warmup", "1", "--height", "96", "--width", "128", "--base-dim", "16",
                 "--rays", "128", "--cpu-seconds", "0"])
     assert t["config"]["parallelism"] == "ddp1" and t["gradient_allreduce_ms"] > 0 and t["collective_backend"].startswith("nccl")
     assert t["loss"] == t["loss"]
@@ -257,7 +257,7 @@ def test_two_gpus_rccl_ray_split_is_bit_equal():
 
 @two_gpus
 def test_two_gpus_rccl_training_ddp():
-    r = _bench(["--workload", "train", "--gpus", "2", "--steps", "2", "--warmup", "1", "--height", "96", "--width", "128",
+    r = _bench(["--workload", "train", "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--height", "96", "--width", "128",
                 "--base-dim", "16", "--rays", "128"])
     assert r["n_gpus"] == 2 and r["config"]["parallelism"] == "ddp2" and r["gradient_allreduce_ms"] > 0
     assert r["collective_backend"].startswith("nccl") and r["loss"] == r["loss"]
