@@ -38,7 +38,7 @@ extern "C" {
 
 /* ABI version, bumped whenever a signature below changes.  Defined here once: surf_abi_version() returns it and the
  * host binding (surf_amd/_lib.py ABI_VERSION) refuses a library that reports a different number. */
-#define SURF_ABI_VERSION 39
+#define SURF_ABI_VERSION 40
 int surf_abi_version(void);
 
 /* Repack NCHW fp32 (n, C<=4, H, W) into texel4 NHWC (n, H, W, 4), zero padding channels >= C. */
@@ -138,6 +138,17 @@ int surf_sdf_lattice_bf16x3(const float* ax, const float* ay, const float* az, i
 int surf_sdf_lattice_f16x2(const float* ax, const float* ay, const float* az, int nx, int ny, int nz, const float* const* h_vols,
                            const int32_t* const* h_tables, const int* h_dims, int n_vol, const void* packed, float* out,
                            float sign, void* stream);
+
+/* The same on the bricks of the narrow band (surf_band_*): out[j * 512 + (lx << 6 | ly << 3 | lz)] = sign * sdf(ax[x], ay[y], az[z])
+ * at lattice point (x, y, z) = 8 (bx, by, bz) + (lx, ly, lz) of brick bricks[j] = (bx nbp + by) nbp + bz, nbp = ceil(res / 8), for
+ * the points with x, y, z < res (the others are not written).  ax / ay / az: res values each (the dense lattice's axes, so
+ * the values are bit-equal to surf_sdf_lattice_*'s).  n_bricks * 512 < 2^31 per call. */
+int surf_sdf_bricks_bf16x3(const float* ax, const float* ay, const float* az, int res, const int32_t* bricks, int64_t n_bricks,
+                           const float* const* h_vols, const int32_t* const* h_tables, const int* h_dims, int n_vol, const void* packed,
+                           float* out, float sign, void* stream);
+int surf_sdf_bricks_f16x2(const float* ax, const float* ay, const float* az, int res, const int32_t* bricks, int64_t n_bricks,
+                          const float* const* h_vols, const int32_t* const* h_tables, const int* h_dims, int n_vol, const void* packed,
+                          float* out, float sign, void* stream);
 
 /*
  * Second-order term of the SDF network (training): grad (n,3) (optional) and smooth (n,3) = H.1, the row sums of the
@@ -648,6 +659,49 @@ int64_t surf_mc_workspace_ints(int64_t n_active);
 int surf_mc_count(const uint8_t* flags, const int32_t* active, int64_t n_active, int32_t* workspace, int32_t* totals, void* stream);
 int surf_mc_emit(const float* u, int nx, int ny, int nz, double isovalue, const uint8_t* flags, const int32_t* active,
                  int64_t n_active, const int32_t* workspace, int32_t* vbase, double* vertices, int32_t* triangles, void* stream);
+
+/*
+ * Narrow-band marching cubes (extract_geometry with render.mesh_extraction = band): the mesh of surf_mc_* on a res^3
+ * lattice, the same arrays in the same order, from the SDF evaluated only in bricks of 8^3 cells near the surface.
+ * Brick b owns lattice points 8b .. 8b+7 per axis and the cells whose origins those are; nbp = ceil(res / 8) bricks per axis
+ * in the table (surf_band_table_size(res) = nbp^3 entries), brick ids (bx nbp + by) nbp + bz.  State on the device:
+ *   table (nbp^3 int32, -1 = not evaluated) -> slot; bricks (slot -> id); vals (slots * 512 fp32, u = -sdf, local point
+ *   lx << 6 | ly << 3 | lz); is_cell (nbp^3 bytes: the brick's cells are meshed; the other evaluated bricks are halo)
+ * Call sequence (the host sizes buffers and runs the growth loop with ONE read of the two counts per pass):
+ *   surf_band_screen   coarse lattice uc ((nbc+1)^3, nbc = ceil((res-1)/8), at lattice indices 0, 8, .., and res-1; cax/cay/caz
+ *                      its axis values) -> mark[id] = 1 for the bricks whose corners change sign (u <= isovalue) or whose
+ *                      min |u - isovalue| <= margin * (brick diagonal) / 2
+ *   loop: surf_band_promote  marked bricks that are no cell bricks yet become ones (they stay marked); they and their forward
+ *                      neighbours not in the table get need[id] = 1
+ *         surf_compact(mark) -> new cell bricks, surf_compact(need) -> bricks to evaluate; stop when no new cell brick
+ *         surf_band_assign  table slots for the bricks to evaluate (clears need) -> evaluate (surf_sdf_bricks_* or
+ *                      surf_band_points + surf_sdf_mlp)
+ *         surf_band_clear(new cell bricks, mark); surf_band_grow: every sign-changing edge of their cells marks the bricks of
+ *                      the cells incident to it
+ *   surf_band_classify -> flags (slots * 512 bytes) as surf_mc_classify's, for edges / cells of cell bricks only
+ *   surf_compact(flags) -> pos; surf_band_keys -> int64 lattice keys (x res + y) res + z; sort them ascending;
+ *   surf_band_rank     sorted keys -> pos (band positions); surf_mc_count(flags, pos) -> workspace, totals
+ *   surf_band_emit     -> vertices / triangles as surf_mc_emit; vbase: slots * 512 int32 scratch
+ * Vertex order: (owner lattice point, axis); triangle order: cell then table order - surf_mc_emit's.  res <= SURF_BAND_MAX_RES.
+ */
+#define SURF_BAND_MAX_RES 8192
+int64_t surf_band_table_size(int res);
+int surf_band_screen(const float* uc, const float* cax, const float* cay, const float* caz, int res, double isovalue, double margin,
+                     uint8_t* mark, void* stream);
+int surf_band_promote(uint8_t* mark, uint8_t* is_cell, const int32_t* table, uint8_t* need, int res, void* stream);
+int surf_band_assign(const int32_t* ids, int64_t m, int32_t slot0, int32_t* table, int32_t* bricks, uint8_t* need, void* stream);
+int surf_band_clear(const int32_t* ids, int64_t m, uint8_t* mark, void* stream);
+int surf_band_grow(const float* vals, const int32_t* table, const uint8_t* is_cell, const int32_t* ids, int64_t m, int res,
+                   double isovalue, uint8_t* mark, void* stream);
+int surf_band_points(const float* ax, const float* ay, const float* az, const int32_t* bricks, int64_t m, int res, float* pts,
+                     void* stream);
+int surf_band_classify(const float* vals, const int32_t* table, const uint8_t* is_cell, const int32_t* bricks, int64_t n_slots,
+                       int res, double isovalue, uint8_t* flags, void* stream);
+int surf_band_keys(const int32_t* pos, int64_t m, const int32_t* bricks, int res, int64_t* keys, void* stream);
+int surf_band_rank(const int64_t* keys, int64_t m, const int32_t* table, int res, int32_t* pos, void* stream);
+int surf_band_emit(const float* vals, const int32_t* table, int res, double isovalue, const uint8_t* flags, const int64_t* keys,
+                   const int32_t* pos, int64_t m, const int32_t* workspace, int32_t* vbase, double* vertices, int32_t* triangles,
+                   void* stream);
 
 /*
  * First-hit face ids of a triangle mesh from one pinhole view, by z-buffer rasterisation (mesh cleaning of the

@@ -52,7 +52,9 @@ def parse_args(argv=None):
                     help="evaluate every (down_rule, kernel_order, transposed_pairing) combination and report the one closest to "
                          "--reference_chamfer")
     ap.add_argument("--sdf_precision", default=None, choices=["f32", "bf16x3", "f16x2"])
-    ap.add_argument("--mesh_resolution", type=int, default=512)
+    ap.add_argument("--mesh_resolution", type=int, default=512, help="lattice points per axis of the mesh (band: up to 8192)")
+    ap.add_argument("--mesh_extraction", default=None, choices=["dense", "band"],
+                    help="model.implicit_surface.render.mesh_extraction: whole lattice or bricks near the surface (same mesh)")
     ap.add_argument("--clean_mesh", action="store_true", help="runner.py --clean_mesh: drop faces outside the dilated masks / frusta")
     ap.add_argument("--downsample_density", type=float, default=0.2)
     ap.add_argument("--patch_size", type=float, default=60)
@@ -87,6 +89,8 @@ def run(args):
             mconf["reg_network"][key] = getattr(args, key)
     if args.sdf_precision is not None:
         mconf["implicit_surface"]["render"]["sdf_precision"] = args.sdf_precision
+    if args.mesh_extraction:
+        mconf["implicit_surface"]["render"]["mesh_extraction"] = args.mesh_extraction
 
     t0 = time.perf_counter()
     loader, _, dataset = get_loader(dconf, "val", False, num_workers=0)

@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("SURF_HIP_LIB", os.path.join(_HERE, "libsurf_hip.so"))
 
 # must equal SURF_ABI_VERSION of include/surf_hip.h (tests/test_host_modules.py compares the two texts); lib() refuses a
 # library built from another header
-ABI_VERSION = 39
+ABI_VERSION = 40
 
 c_f32p = ctypes.c_void_p
 c_ptr = ctypes.c_void_p
@@ -39,6 +39,8 @@ SIGNATURES = {
     "surf_sdf_mlp_bf16x3_dn": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     "surf_sdf_lattice_bf16x3": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_float, c_ptr]),
     "surf_sdf_lattice_f16x2": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_float, c_ptr]),
+    "surf_sdf_bricks_bf16x3": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_float, c_ptr]),
+    "surf_sdf_bricks_f16x2": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_float, c_ptr]),
     "surf_sdf_mlp_f16x2_dn": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     "surf_blend_split_dn": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_int,
                                     c_ptr, c_ptr, c_ptr, c_ptr]),
@@ -79,6 +81,17 @@ SIGNATURES = {
     "surf_mc_workspace_ints": (c_i64, [c_i64]),
     "surf_mc_count": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
     "surf_mc_emit": (c_int, [c_ptr, c_int, c_int, c_int, ctypes.c_double, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "surf_band_table_size": (c_i64, [c_int]),
+    "surf_band_screen": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, ctypes.c_double, ctypes.c_double, c_ptr, c_ptr]),
+    "surf_band_promote": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr]),
+    "surf_band_assign": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "surf_band_clear": (c_int, [c_ptr, c_i64, c_ptr, c_ptr]),
+    "surf_band_grow": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, ctypes.c_double, c_ptr, c_ptr]),
+    "surf_band_points": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr]),
+    "surf_band_classify": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, ctypes.c_double, c_ptr, c_ptr]),
+    "surf_band_keys": (c_int, [c_ptr, c_i64, c_ptr, c_int, c_ptr, c_ptr]),
+    "surf_band_rank": (c_int, [c_ptr, c_i64, c_ptr, c_int, c_ptr, c_ptr]),
+    "surf_band_emit": (c_int, [c_ptr, c_ptr, c_int, ctypes.c_double, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     "surf_raster_first_hit": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
     "surf_composite": (c_int, [c_ptr] * 9 + [c_int, c_int, c_float, c_float] + [c_ptr] * 13),
     "surf_upsample_bilinear_t4": (c_int, [c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),

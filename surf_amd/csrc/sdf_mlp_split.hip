@@ -654,7 +654,10 @@ __device__ __forceinline__ void pad_chunks(const Ctx& c, const FragT<P::NP>* any
   }
 }
 
-template <class P, bool GRAD>
+// BRICK (forward only; surf_sdf_bricks_*): point i is local point i & 511 of brick idx[i >> 9] of the narrow-band lattice
+// (mesh_band.hip: brick ids (bx nbp + by) nbp + bz with nbp = lat_nz, lattice points 0 .. lat_ny - 1 per axis), coordinates
+// from the three axis arrays as in lattice mode; points past the lattice's upper faces are masked out.
+template <class P, bool GRAD, bool BRICK = false>
 __global__ __launch_bounds__(WPB * 64, P::occ(GRAD)) void sdf_mlp_split_kernel(SdfArgs a) {
   typedef FragT<P::NP> Frag;
   constexpr int NS = P::nslot(GRAD), NCH = n_chunks<P>(GRAD);
@@ -703,16 +706,28 @@ __global__ __launch_bounds__(WPB * 64, P::occ(GRAD)) void sdf_mlp_split_kernel(S
     const int64_t tile = round * WPB + c.wave;
     const int64_t slot0 = tile * TILE + (c.lane & 31);
     const int64_t sc = slot0 < n_pts ? slot0 : n_pts - 1;
-    const int64_t i = a.idx ? (int64_t)a.idx[sc] : sc;
-    const bool active = (slot0 < n_pts) && (!a.mask || a.mask[i] != 0);
+    int64_t i;
+    bool active;
     float px, py, pz;
-    if (a.pts) {
-      px = a.pts[i * 3 + 0]; py = a.pts[i * 3 + 1]; pz = a.pts[i * 3 + 2];
-    } else {  // lattice mode: the point from its linear index (n < 2^31, checked at launch)
-      const uint32_t ii = (uint32_t)i, yz = ii / (uint32_t)a.lat_nz;
-      px = a.lat_axes[0][yz / (uint32_t)a.lat_ny];
-      py = a.lat_axes[1][yz % (uint32_t)a.lat_ny];
-      pz = a.lat_axes[2][ii % (uint32_t)a.lat_nz];
+    if constexpr (BRICK) {  // n < 2^31, checked at launch
+      i = sc;
+      const uint32_t id = (uint32_t)a.idx[sc >> 9], l = (uint32_t)sc & 511u, nb = (uint32_t)a.lat_nz, last = (uint32_t)a.lat_ny - 1u;
+      const uint32_t gx = id / (nb * nb) * 8u + (l >> 6), gy = id / nb % nb * 8u + ((l >> 3) & 7u), gz = id % nb * 8u + (l & 7u);
+      active = (slot0 < n_pts) && gx <= last && gy <= last && gz <= last;
+      px = a.lat_axes[0][gx < last ? gx : last];
+      py = a.lat_axes[1][gy < last ? gy : last];
+      pz = a.lat_axes[2][gz < last ? gz : last];
+    } else {
+      i = a.idx ? (int64_t)a.idx[sc] : sc;
+      active = (slot0 < n_pts) && (!a.mask || a.mask[i] != 0);
+      if (a.pts) {
+        px = a.pts[i * 3 + 0]; py = a.pts[i * 3 + 1]; pz = a.pts[i * 3 + 2];
+      } else {  // lattice mode: the point from its linear index (n < 2^31, checked at launch)
+        const uint32_t ii = (uint32_t)i, yz = ii / (uint32_t)a.lat_nz;
+        px = a.lat_axes[0][yz / (uint32_t)a.lat_ny];
+        py = a.lat_axes[1][yz % (uint32_t)a.lat_ny];
+        pz = a.lat_axes[2][ii % (uint32_t)a.lat_nz];
+      }
     }
 
     Frag ef[2], pf[2];
@@ -1016,7 +1031,7 @@ int pack_weights(const float* const* h_W, const float* const* h_b, unsigned char
   return 0;
 }
 
-struct Lattice { const float* ax[3]; int ny, nz; float sign; };
+struct Lattice { const float* ax[3]; int ny, nz; float sign; bool bricks; };
 template <class P>
 int launch(const float* pts, const uint8_t* mask, const int32_t* idx, int64_t n, const float* const* h_vols,
            const int32_t* const* h_tables, const int* h_dims, int n_vol, const void* packed, float* sdf, float* grad,
@@ -1030,9 +1045,10 @@ int launch(const float* pts, const uint8_t* mask, const int32_t* idx, int64_t n,
   a.scratch = (float*)scratch;
   a.lat_axes[0] = a.lat_axes[1] = a.lat_axes[2] = nullptr; a.lat_ny = a.lat_nz = 1; a.out_sign = 1.0f;
   if (lat) {
-    if (grad || mask || idx || d_n || n >= (int64_t)1 << 31 || lat->ny < 1 || lat->nz < 1 || !lat->ax[0] || !lat->ax[1] || !lat->ax[2]) return SURF_E_ARG;
+    if (grad || mask || (idx != nullptr) != lat->bricks || d_n || n >= (int64_t)1 << 31 || lat->ny < 1 || lat->nz < 1 || !lat->ax[0] || !lat->ax[1] || !lat->ax[2]) return SURF_E_ARG;
     for (int k = 0; k < 3; ++k) a.lat_axes[k] = lat->ax[k];
     a.lat_ny = lat->ny; a.lat_nz = lat->nz; a.out_sign = lat->sign;
+    if (lat->bricks) a.idx = idx;  // the brick list
   }
   for (int s = 0; s < SURF_MAX_STAGES; ++s) {
     a.vols[s] = s < n_vol ? h_vols[s] : h_vols[0];
@@ -1042,7 +1058,9 @@ int launch(const float* pts, const uint8_t* mask, const int32_t* idx, int64_t n,
     if (s < n_vol && h_dims[s] > 1024) return SURF_E_LIMIT;  // 32-bit table indices (gather_features)
   }
   dim3 grid(grid_blocks<P>(n, grad != nullptr)), block(WPB * 64);
-  if (grad)
+  if (lat && lat->bricks)
+    hipLaunchKernelGGL((sdf_mlp_split_kernel<P, false, true>), grid, block, 0, (hipStream_t)stream, a);
+  else if (grad)
     hipLaunchKernelGGL((sdf_mlp_split_kernel<P, true>), grid, block, 0, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL((sdf_mlp_split_kernel<P, false>), grid, block, 0, (hipStream_t)stream, a);
@@ -1055,8 +1073,21 @@ template <class P>
 int launch_lattice(const float* ax, const float* ay, const float* az, int nx, int ny, int nz, const float* const* h_vols,
                    const int32_t* const* h_tables, const int* h_dims, int n_vol, const void* packed, float* out, float sign, void* stream) {
   if (nx < 1 || ny < 1 || nz < 1) return SURF_E_ARG;
-  const Lattice lat = {{ax, ay, az}, ny, nz, sign};
+  const Lattice lat = {{ax, ay, az}, ny, nz, sign, false};
   return launch<P>(nullptr, nullptr, nullptr, (int64_t)nx * ny * nz, h_vols, h_tables, h_dims, n_vol, packed, out, nullptr, nullptr, stream,
+                   nullptr, &lat);
+}
+
+// the narrow band of extract_geometry (mesh_band.hip): out[j * 512 + l] = sign * sdf at local point l of brick bricks[j] of the
+// res^3 lattice on the axes ax / ay / az (res values each); points past the lattice's upper faces are not written
+template <class P>
+int launch_bricks(const float* ax, const float* ay, const float* az, int res, const int32_t* bricks, int64_t n_bricks,
+                  const float* const* h_vols, const int32_t* const* h_tables, const int* h_dims, int n_vol, const void* packed, float* out,
+                  float sign, void* stream) {
+  if (res < 2 || res > SURF_BAND_MAX_RES || !bricks || n_bricks <= 0) return SURF_E_ARG;
+  if (n_bricks * 512 >= (int64_t)1 << 31) return SURF_E_LIMIT;  // the caller splits longer lists
+  const Lattice lat = {{ax, ay, az}, res, (res + 7) / 8, sign, true};
+  return launch<P>(nullptr, nullptr, bricks, n_bricks * 512, h_vols, h_tables, h_dims, n_vol, packed, out, nullptr, nullptr, stream,
                    nullptr, &lat);
 }
 
@@ -1110,12 +1141,22 @@ extern "C" int surf_sdf_lattice_bf16x3(const float* ax, const float* ay, const f
                                        float sign, void* stream) {
   return launch_lattice<PolBf3>(ax, ay, az, nx, ny, nz, h_vols, h_tables, h_dims, n_vol, packed, out, sign, stream);
 }
+extern "C" int surf_sdf_bricks_bf16x3(const float* ax, const float* ay, const float* az, int res, const int32_t* bricks, int64_t n_bricks,
+                                      const float* const* h_vols, const int32_t* const* h_tables, const int* h_dims, int n_vol,
+                                      const void* packed, float* out, float sign, void* stream) {
+  return launch_bricks<PolBf3>(ax, ay, az, res, bricks, n_bricks, h_vols, h_tables, h_dims, n_vol, packed, out, sign, stream);
+}
 
 #else
 extern "C" int surf_sdf_lattice_f16x2(const float* ax, const float* ay, const float* az, int nx, int ny, int nz, const float* const* h_vols,
                                       const int32_t* const* h_tables, const int* h_dims, int n_vol, const void* packed, float* out,
                                       float sign, void* stream) {
   return launch_lattice<PolH2>(ax, ay, az, nx, ny, nz, h_vols, h_tables, h_dims, n_vol, packed, out, sign, stream);
+}
+extern "C" int surf_sdf_bricks_f16x2(const float* ax, const float* ay, const float* az, int res, const int32_t* bricks, int64_t n_bricks,
+                                     const float* const* h_vols, const int32_t* const* h_tables, const int* h_dims, int n_vol,
+                                     const void* packed, float* out, float sign, void* stream) {
+  return launch_bricks<PolH2>(ax, ay, az, res, bricks, n_bricks, h_vols, h_tables, h_dims, n_vol, packed, out, sign, stream);
 }
 extern "C" int64_t surf_sdf_f16_packed_bytes(void) { return stream_bytes<PolH2>() + TAIL_FLOATS * 4; }
 extern "C" int64_t surf_sdf_f16_scratch_bytes(int64_t n_points) { return scratch_bytes<PolH2>(n_points); }

@@ -312,7 +312,9 @@ struct SdfArgs {
   float* grad;
   float* scratch;
   // lattice mode (pts == nullptr, forward only; surf_sdf_lattice_*): point i = (ax[i / (ny nz)], ay[(i / nz) % ny], az[i % nz]) from
-  // the three axis arrays - no point tensor is written or read - and sdf[i] = out_sign * value (extract_geometry's u = -sdf)
+  // the three axis arrays - no point tensor is written or read - and sdf[i] = out_sign * value (extract_geometry's u = -sdf).
+  // Brick mode (the kernel's BRICK instantiation; surf_sdf_bricks_*): idx = brick list, lat_ny = lattice points per axis,
+  // lat_nz = bricks per axis of the brick table; point i = local point i & 511 of brick idx[i >> 9]
   const float* lat_axes[3];
   int lat_ny, lat_nz;
   float out_sign;

@@ -177,6 +177,13 @@ def _occupied_list(rec, key):
     return lst
 
 
+MESH_EXTRACTIONS = ("dense", "band")
+# render.mesh_band_margin default: the coarse screen keeps a brick whose corner values come within margin * (half its diagonal)
+# of the isovalue, i.e. it assumes |grad u| <= margin.  Measured maximum of the finite-difference |grad u| on the bench scene's
+# 512^3 lattice: 1.63 (1.44 near the surface; DESIGN.md K13b, scripts/time_mesh_band.py), rounded up
+MESH_BAND_MARGIN = 2.0
+
+
 class ImplicitSurface(nn.Module):
     """implicit_surface.py:50-436 (inference semantics)."""
 
@@ -199,6 +206,15 @@ class ImplicitSurface(nn.Module):
         self.blend_precision = confs.get_string("render.blend_precision", ops.BLEND_DEFAULT)
         if self.blend_precision not in ops.BLEND_PRECISIONS:
             raise ValueError(f"render.blend_precision must be one of {ops.BLEND_PRECISIONS}, got {self.blend_precision!r}")
+        # how extract_geometry builds the mesh (MESH_EXTRACTIONS): "dense" = the SDF and marching cubes on the whole lattice (the
+        # reference's sweep, default); "band" = only 8^3-cell bricks near the surface (same arrays unless a surface component has
+        # no brick that passes the coarse screen: INTEGRATION.md).  mesh_band_margin: the Lipschitz bound of u the screen assumes
+        self.mesh_extraction = confs.get_string("render.mesh_extraction", "dense")
+        if self.mesh_extraction not in MESH_EXTRACTIONS:
+            raise ValueError(f"render.mesh_extraction must be one of {MESH_EXTRACTIONS}, got {self.mesh_extraction!r}")
+        self.mesh_band_margin = confs.get_float("render.mesh_band_margin", MESH_BAND_MARGIN)
+        if not self.mesh_band_margin >= 0.0:
+            raise ValueError(f"render.mesh_band_margin must be >= 0, got {self.mesh_band_margin!r}")
         self._packed = None
         self.kernel_events = None          # bench.py: list receiving (name, start, end) HIP event triples
         self.active_samples_log = None     # bench.py: list receiving the active-sample count of every render call
@@ -531,20 +547,106 @@ class ImplicitSurface(nn.Module):
                 self.kernel_events.append(("sdf_grid", a, b))
         return u
 
-    def extract_geometry(self, volumes, sparse_idxes, bound_min, bound_max, resolution, threshold, scene=None):
+    def _lattice_axes(self, bound_min, bound_max, resolution, dev):
+        """sdf_grid's three axis arrays (torch.linspace's values, :338-340)."""
+        bmin = bound_min.detach().to("cpu", torch.float32)
+        bmax = bound_max.detach().to("cpu", torch.float32)
+        return [torch.linspace(float(bmin[a]), float(bmax[a]), resolution).to(dev) for a in range(3)]
+
+    def _timed_event(self, name, fn):
+        if self.kernel_events is None:
+            return fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = fn()
+        b.record()
+        self.kernel_events.append((name, a, b))
+        return out
+
+    def _band(self, scene, bound_min, bound_max, resolution, margin=None, threshold=0.0):
+        """The evaluated narrow band of extract_geometry's lattice (ops.Band): coarse screen on the lattice points 0, 8, 16, ..,
+        resolution - 1 of every axis (exact lattice values), then the growth loop with the SDF evaluated brick by brick - the
+        split kernels' brick mode, or (f32) brick points through the fp32 kernel - at the floats sdf_grid evaluates."""
+        dev = scene.device
+        margin = self.mesh_band_margin if margin is None else float(margin)
+        if not margin >= 0.0:
+            raise ValueError(f"mesh band margin must be >= 0, got {margin!r}")
+        sdf_w, _ = self.packed_weights(dev)
+        axes = self._lattice_axes(bound_min, bound_max, resolution, dev)
+        idx = torch.tensor(ops.band_coarse_index(resolution), dtype=torch.long, device=dev)
+        caxes = [ax[idx].contiguous() for ax in axes]
+        nc = len(idx)
+        split = self.sdf_precision != "f32"
+
+        def coarse():
+            uc = torch.empty(nc, nc, nc, dtype=torch.float32, device=dev)
+            if split:
+                ops.sdf_lattice(caxes, scene.sv, sdf_w, uc, 0, nc, sign=-1.0)
+            else:
+                slab = max(1, (1 << 24) // (nc * nc))
+                for x0 in range(0, nc, slab):
+                    nx = min(slab, nc - x0)
+                    xx, yy, zz = torch.meshgrid(caxes[0][x0:x0 + nx], caxes[1], caxes[2], indexing="ij")
+                    pts = torch.stack([xx.reshape(-1), yy.reshape(-1), zz.reshape(-1)], dim=-1).contiguous()
+                    sdf, _ = ops.sdf_mlp(pts, scene.sv, sdf_w, want_grad=False)
+                    uc[x0:x0 + nx] = -sdf.view(nx, nc, nc)
+            return uc
+
+        def evaluate(bricks, out):
+            if split:
+                self._timed_event("band_sdf", lambda: ops.sdf_bricks(axes, scene.sv, sdf_w, bricks, resolution, out, sign=-1.0))
+                return
+            for j0 in range(0, int(bricks.shape[0]), ops.BAND_F32_BRICKS):
+                part = bricks[j0:j0 + ops.BAND_F32_BRICKS]
+
+                def one():
+                    sdf, _ = ops.sdf_mlp(ops.band_points(axes, part, resolution), scene.sv, sdf_w, want_grad=False)
+                    torch.neg(sdf, out=out[j0 * 512:(j0 + part.shape[0]) * 512])
+                self._timed_event("band_sdf", one)
+
+        uc = self._timed_event("band_sdf", coarse)
+        mark = ops.band_screen(uc, caxes, resolution, threshold, margin)
+        del uc
+        band = ops.band_grow(resolution, threshold, mark, evaluate)
+        band.stats["coarse_points"] = nc ** 3
+        band.stats["points_evaluated"] = nc ** 3 + band.stats["band_points"]
+        return band
+
+    def sdf_band(self, scene, bound_min, bound_max, resolution, margin=None, threshold=0.0):
+        """The narrow band of extract_geometry's lattice (render.mesh_extraction = band): (bricks (m, 3) int32 brick coordinates -
+        brick (bx, by, bz) owns the lattice points 8 (bx, by, bz) + (0..7)^3 -, values (m, 512) fp32 u = -sdf brick-major (local
+        point lx * 64 + ly * 8 + lz; NaN past the lattice's upper faces), stats dict: bricks screened / seeded / grown /
+        evaluated, growth iterations (passes that added cell bricks, the seed pass included), points evaluated).  margin: None = render.mesh_band_margin; threshold: the isovalue
+        of the screen and the growth."""
+        band = self._band(scene, bound_min, bound_max, resolution, margin, threshold)
+        _, nbp = ops.band_dims(resolution)
+        ids = band.bricks.long()
+        coords = torch.stack([ids // (nbp * nbp), (ids // nbp) % nbp, ids % nbp], dim=1).to(torch.int32)
+        return coords, band.values.view(-1, 512), dict(band.stats)
+
+    def extract_geometry(self, volumes, sparse_idxes, bound_min, bound_max, resolution, threshold, scene=None, mesh_extraction=None):
         """implicit_surface.py:337-357.  Callable with the reference's signature (volumes: (N_s, 7) rows fine -> coarse,
-        sparse_idxes: their index tables) or with prepared SceneVolumes (`scene=`)."""
-        from .marching_cubes import marching_cubes
+        sparse_idxes: their index tables) or with prepared SceneVolumes (`scene=`).  mesh_extraction: "dense" (the whole
+        lattice) or "band" (bricks near the surface, the same arrays: see _band); None = render.mesh_extraction."""
+        from .marching_cubes import marching_cubes, marching_cubes_band
+        mode = self.mesh_extraction if mesh_extraction is None else mesh_extraction
+        if mode not in MESH_EXTRACTIONS:
+            raise ValueError(f"mesh_extraction must be one of {MESH_EXTRACTIONS}, got {mode!r}")
         if scene is None:
             if volumes is None or sparse_idxes is None:
                 raise ValueError("extract_geometry needs either (volumes, sparse_idxes) or scene=SceneVolumes")
             scene = _LatticeScene(volumes, sparse_idxes)
-        u = self.sdf_grid(scene, bound_min, bound_max, resolution)
+        if mode == "band":
+            band = self._band(scene, bound_min, bound_max, resolution, threshold=threshold)
+        else:
+            u = self.sdf_grid(scene, bound_min, bound_max, resolution)
         b_max_np = bound_max.detach().cpu().numpy()
         b_min_np = bound_min.detach().cpu().numpy()
         # vertices / (resolution - 1.0) * (b_max - b_min) + b_min (:354-356) in float64 on the device, before the one copy to the host
-        vertices, triangles = marching_cubes(u, threshold, rescale=(resolution - 1.0, (b_max_np - b_min_np).astype(np.float64),
-                                                                     b_min_np.astype(np.float64)))
+        rescale = (resolution - 1.0, (b_max_np - b_min_np).astype(np.float64), b_min_np.astype(np.float64))
+        if mode == "band":
+            return self._timed_event("band_mc", lambda: marching_cubes_band(band, threshold, rescale=rescale))
+        vertices, triangles = marching_cubes(u, threshold, rescale=rescale)
         return vertices, triangles
 
     def validate(self, rays_o, rays_d, near, far, scene, bound_min, bound_max, hw, cos_anneal_ratio=1.0, step=None,
@@ -582,7 +684,8 @@ class ImplicitSurface(nn.Module):
         flat = torch.cat([color.reshape(-1), img.reshape(-1), nimg.reshape(-1), torch.cat(sdeps).reshape(-1), torch.cat(rdeps).reshape(-1)])
         host, copied = self._to_host_async(flat)
         if extract_geometry:
-            v, t = self.extract_geometry(None, None, bound_min, bound_max, mesh_resolution, threshold, scene=scene)
+            v, t = self.extract_geometry(None, None, bound_min, bound_max, mesh_resolution, threshold, scene=scene,
+                                         mesh_extraction=self.mesh_extraction)
             outputs["vertices"], outputs["triangles"] = v, t
         if copied is not None:
             copied.synchronize()

@@ -33,6 +33,17 @@ def marching_cubes(u, threshold=0.0, rescale=None):
         u = torch.from_numpy(np.ascontiguousarray(np.asarray(u, dtype=np.float32))).cuda()
     u = u.float().contiguous()
     v, t = ops.marching_cubes(u, float(threshold))
+    return _to_numpy(v, t, rescale)
+
+
+def marching_cubes_band(band, threshold=0.0, rescale=None):
+    """marching_cubes on an evaluated narrow band (ops.Band, ImplicitSurface's band extraction): the same arrays the dense
+    lattice gives, as numpy arrays, with the same device-side rescale and the same one copy to the host."""
+    v, t = ops.marching_cubes_band(band, float(threshold))
+    return _to_numpy(v, t, rescale)
+
+
+def _to_numpy(v, t, rescale):
     if rescale is not None:
         res_m1, span, lo = rescale
         v = v / float(res_m1) * torch.as_tensor(span, dtype=torch.float64, device=v.device)[None, :] \

@@ -1344,6 +1344,177 @@ def marching_cubes(u, isovalue=0.0):
 
 
 # ------------------------------------------------------------------------------------------------
+# narrow-band marching cubes (mesh_band.hip): the dense mesh from the SDF in 8^3-cell bricks near the surface
+# ------------------------------------------------------------------------------------------------
+
+BAND_SPLIT_BRICKS = ((1 << 31) - 1) // 512     # bricks per launch of the split kernels' brick mode (< 2^31 points)
+BAND_F32_BRICKS = (1 << 24) // 512              # bricks per point tensor of the fp32 path (sdf_grid's 2^24 points per launch)
+
+
+def band_dims(resolution):
+    """(bricks per axis that hold cells, bricks per axis of the brick table) of a resolution^3 lattice."""
+    n = int(resolution)
+    return (n - 1 + 7) // 8, (n + 7) // 8
+
+
+def band_coarse_index(resolution):
+    """Lattice indices of the coarse screen along one axis: 0, 8, 16, .. (one per cell brick) and resolution - 1."""
+    n = int(resolution)
+    return list(range(0, n - 1, 8)) + [n - 1]
+
+
+def sdf_bricks(axes, volumes, packed, bricks, resolution, out, sign=-1.0):
+    """out[j * 512 + l] = sign * sdf at local point l of brick bricks[j] of the resolution^3 lattice on `axes` (the lattice's
+    three axis arrays): the split kernel's brick mode, values bit-equal to sdf_lattice's.  Points past the upper faces are not
+    written.  Split precisions only; long lists are split into launches of < 2^31 points."""
+    precision = sdf_packed_precision(packed)
+    if precision == "f32":
+        raise ValueError("sdf_bricks: bf16x3 / f16x2 weights only (the fp32 path evaluates band_points with sdf_mlp)")
+    for ax in axes:
+        _chk(ax, torch.float32, "lattice axis")
+    _chk(bricks, torch.int32, "bricks")
+    _chk(out, torch.float32, "brick values")
+    m = int(bricks.shape[0])
+    assert out.numel() >= m * 512
+    name = f"surf_sdf_bricks_{precision}"
+    fn = getattr(_lib.lib(), name)
+    for j0 in range(0, m, BAND_SPLIT_BRICKS):
+        k = min(BAND_SPLIT_BRICKS, m - j0)
+        rc = fn(_p(axes[0]), _p(axes[1]), _p(axes[2]), int(resolution), _p(bricks[j0:]), k, volumes._vp, volumes._tp, volumes._dp,
+                volumes.n, _p(packed), _p(out[j0 * 512:]), ctypes.c_float(sign), _stream())
+        _lib.check(rc, name)
+
+
+def band_points(axes, bricks, resolution):
+    """(len(bricks) * 512, 3) fp32 points of the bricks' lattice points, brick-major (the floats meshgrid of `axes` gives);
+    points past the upper faces repeat the last lattice point."""
+    for ax in axes:
+        _chk(ax, torch.float32, "lattice axis")
+    _chk(bricks, torch.int32, "bricks")
+    m = int(bricks.shape[0])
+    pts = torch.empty(m * 512, 3, dtype=torch.float32, device=bricks.device)
+    _lib.check(_lib.lib().surf_band_points(_p(axes[0]), _p(axes[1]), _p(axes[2]), _p(bricks), m, int(resolution), _p(pts), _stream()),
+               "surf_band_points")
+    return pts
+
+
+def band_screen(uc, caxes, resolution, isovalue, margin):
+    """Seed marks (brick-table bytes) of the cell bricks whose coarse corners (uc: the lattice at band_coarse_index on every axis,
+    caxes: its axis values) change sign or come within margin * (brick diagonal) / 2 of the isovalue."""
+    _chk(uc, torch.float32, "coarse lattice")
+    for ax in caxes:
+        _chk(ax, torch.float32, "coarse axis")
+    L = _lib.lib()
+    mark = torch.zeros(int(L.surf_band_table_size(int(resolution))), dtype=torch.uint8, device=uc.device)
+    _lib.check(L.surf_band_screen(_p(uc), _p(caxes[0]), _p(caxes[1]), _p(caxes[2]), int(resolution), ctypes.c_double(float(isovalue)),
+                                  ctypes.c_double(float(margin)), _p(mark), _stream()), "surf_band_screen")
+    return mark
+
+
+class Band:
+    """The evaluated narrow band of a resolution^3 lattice (mesh_band.hip's state): table (nbp^3 int32: brick id -> slot or -1),
+    is_cell (nbp^3 bytes: the brick's cells are meshed), bricks (slot -> brick id), values (slot * 512 + local point: u = -sdf;
+    NaN past the upper faces) and the growth statistics."""
+
+    def __init__(self, resolution, table, is_cell, bricks, values, stats):
+        self.resolution, self.table, self.is_cell, self.bricks, self.values, self.stats = resolution, table, is_cell, bricks, values, stats
+
+    @property
+    def n_slots(self):
+        return int(self.bricks.shape[0])
+
+
+def band_grow(resolution, isovalue, mark, evaluate):
+    """The growth loop: mark (band_screen's seeds, consumed) -> Band.  evaluate(bricks (k,) int32, out (k * 512,) fp32) fills the
+    values of the listed bricks.  Every pass promotes the marked bricks to cell bricks, evaluates them and their forward halo,
+    and marks the bricks of every cell incident to a sign-changing edge of their cells; it ends when a pass finds no new cell
+    brick.  One host read per pass (the two counts)."""
+    L = _lib.lib()
+    dev = mark.device
+    n = int(resolution)
+    nt = int(L.surf_band_table_size(n))
+    _chk(mark, torch.uint8, "mark")
+    assert mark.numel() == nt
+    iso = ctypes.c_double(float(isovalue))
+    table = torch.full((nt,), -1, dtype=torch.int32, device=dev)
+    is_cell = torch.zeros(nt, dtype=torch.uint8, device=dev)
+    need = torch.zeros(nt, dtype=torch.uint8, device=dev)
+    ws = torch.empty(L.surf_compact_workspace_ints(nt), dtype=torch.int32, device=dev)
+    new_cell = torch.empty(nt, dtype=torch.int32, device=dev)
+    new_eval = torch.empty(nt, dtype=torch.int32, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    cap = 1024
+    bricks = torch.empty(cap, dtype=torch.int32, device=dev)
+    values = torch.full((cap * 512,), float("nan"), dtype=torch.float32, device=dev)
+    n_slots, passes, seeded, grown = 0, 0, 0, 0
+    for _ in range(nt + 1):                       # every pass but the last adds a cell brick
+        st = _stream()
+        _lib.check(L.surf_band_promote(_p(mark), _p(is_cell), _p(table), _p(need), n, st), "surf_band_promote")
+        _lib.check(L.surf_compact(_p(mark), nt, _p(ws), _p(new_cell), _p(counts), st), "surf_compact")
+        _lib.check(L.surf_compact(_p(need), nt, _p(ws), _p(new_eval), _p(counts[1:]), st), "surf_compact")
+        n_cell, n_eval = (int(v) for v in counts.tolist())            # the pass's one host read
+        if n_cell == 0:
+            break
+        if n_slots + n_eval > cap:
+            cap = max(2 * cap, n_slots + n_eval)
+            b2 = torch.empty(cap, dtype=torch.int32, device=dev)
+            v2 = torch.full((cap * 512,), float("nan"), dtype=torch.float32, device=dev)
+            b2[:n_slots] = bricks[:n_slots]
+            v2[:n_slots * 512] = values[:n_slots * 512]
+            bricks, values = b2, v2
+        _lib.check(L.surf_band_assign(_p(new_eval), n_eval, n_slots, _p(table), _p(bricks), _p(need), st), "surf_band_assign")
+        if n_eval:
+            evaluate(bricks[n_slots:n_slots + n_eval], values[n_slots * 512:(n_slots + n_eval) * 512])
+        n_slots += n_eval
+        st = _stream()
+        _lib.check(L.surf_band_clear(_p(new_cell), n_cell, _p(mark), st), "surf_band_clear")
+        _lib.check(L.surf_band_grow(_p(values), _p(table), _p(is_cell), _p(new_cell), n_cell, n, iso, _p(mark), st), "surf_band_grow")
+        if passes == 0:
+            seeded = n_cell
+        else:
+            grown += n_cell
+        passes += 1
+    nbc, _ = band_dims(n)
+    stats = {"bricks_screened": nbc ** 3, "bricks_seeded": seeded, "bricks_grown": grown, "bricks_evaluated": n_slots,
+             "growth_iterations": passes, "band_points": n_slots * 512}
+    return Band(n, table, is_cell, bricks[:n_slots], values[:n_slots * 512], stats)
+
+
+def marching_cubes_band(band, isovalue=0.0):
+    """marching_cubes on a Band: (vertices (nv, 3) float64, triangles (nt, 3) int32) device tensors in lattice-index units, the
+    arrays marching_cubes returns on the dense lattice (same order) for every surface component that has a cell brick.
+    Two host syncs size the outputs (number of flagged points, then vertex / triangle totals)."""
+    L = _lib.lib()
+    dev = band.values.device
+    n, ns = band.resolution, band.n_slots
+    iso = ctypes.c_double(float(isovalue))
+    empty = torch.zeros(0, 3, dtype=torch.float64, device=dev), torch.zeros(0, 3, dtype=torch.int32, device=dev)
+    if ns == 0:
+        return empty
+    flags = torch.empty(ns * 512, dtype=torch.uint8, device=dev)
+    _lib.check(L.surf_band_classify(_p(band.values), _p(band.table), _p(band.is_cell), _p(band.bricks), ns, n, iso, _p(flags), _stream()),
+               "surf_band_classify")
+    pos = compact(flags)
+    m = int(pos.shape[0])
+    if m == 0:
+        return empty
+    keys = torch.empty(m, dtype=torch.int64, device=dev)
+    _lib.check(L.surf_band_keys(_p(pos), m, _p(band.bricks), n, _p(keys), _stream()), "surf_band_keys")
+    keys = torch.sort(keys).values                       # dense order: ascending lattice keys
+    _lib.check(L.surf_band_rank(_p(keys), m, _p(band.table), n, _p(pos), _stream()), "surf_band_rank")
+    ws = torch.empty(L.surf_mc_workspace_ints(m), dtype=torch.int32, device=dev)
+    totals = torch.empty(2, dtype=torch.int32, device=dev)
+    _lib.check(L.surf_mc_count(_p(flags), _p(pos), m, _p(ws), _p(totals), _stream()), "surf_mc_count")
+    n_v, n_t = (int(v) for v in totals.tolist())
+    vertices = torch.empty(n_v, 3, dtype=torch.float64, device=dev)
+    triangles = torch.empty(n_t, 3, dtype=torch.int32, device=dev)
+    vbase = torch.empty(ns * 512, dtype=torch.int32, device=dev)
+    _lib.check(L.surf_band_emit(_p(band.values), _p(band.table), n, iso, _p(flags), _p(keys), _p(pos), m, _p(ws), _p(vbase), _p(vertices),
+                                _p(triangles), _stream()), "surf_band_emit")
+    return vertices, triangles
+
+
+# ------------------------------------------------------------------------------------------------
 # sparse 3D U-Net pieces (reg_network.py)
 # ------------------------------------------------------------------------------------------------
 
