@@ -38,7 +38,7 @@ extern "C" {
 
 /* ABI version, bumped whenever a signature below changes.  Defined here once: surf_abi_version() returns it and the
  * host binding (surf_amd/_lib.py ABI_VERSION) refuses a library that reports a different number. */
-#define SURF_ABI_VERSION 40
+#define SURF_ABI_VERSION 41
 int surf_abi_version(void);
 
 /* Repack NCHW fp32 (n, C<=4, H, W) into texel4 NHWC (n, H, W, 4), zero padding channels >= C. */
@@ -712,6 +712,34 @@ int surf_band_emit(const float* vals, const int32_t* table, int res, double isov
  */
 int surf_raster_first_hit(const float* vertices, const int32_t* faces, int64_t n_faces, const float* h_K, const float* h_w2c,
                           int h, int w, int Hup, int Wup, unsigned long long* zbuf, void* stream);
+
+/*
+ * DTU Chamfer evaluation on the device (surf_amd/evaluation/dtu_eval.py, device="gpu"; dtu_eval.hip).  fp64 throughout, in
+ * numpy's operation order; every output equals the numpy / scikit-learn evaluator's bit for bit.
+ *   surf_dtu_sample_count / _write: sample_mesh_points' lattice samples of every triangle.  vertices (nv,3) fp64, triangles
+ *     (n_tri,3) int64; counts (n_tri) int64 samples per triangle; out + 3*offsets[t] receives triangle t's samples, offsets
+ *     the exclusive scan of counts (the caller places the vertices in front).
+ *   surf_dtu_cell_keys: key (cx*ny + cy)*nz + cz of the cell floor((p - lo) / cell) of every point, clamped to the grid
+ *     (nx, ny, nz <= 2^21; the thinning grid uses 2^21 on every axis, i.e. (cx << 42) | (cy << 21) | cz).
+ *   surf_dtu_thin_round: one round of the parallel greedy thinning (downsample_points).  The n samples in cell order:
+ *     sorted_points (n,3), sorted_index (n) their position in the shuffled order (ascending inside a cell), sorted_cell (n)
+ *     their cell's position in cell_keys (n_cells distinct keys, ascending), cell_start (n_cells+1).  state (n, by shuffled
+ *     position) 0 undecided / 1 kept / 2 removed, updated in place; *undecided is zeroed, then counts the samples still
+ *     undecided.  Neighbours: (dx*dx + dy*dy) + dz*dz <= thresh*thresh.
+ *   surf_dtu_nearest: out[q] = distance from queries[q] to the nearest of the reference points if < max_dist, else +inf.
+ *     sorted_ref (r,3) in cell order of the dense (nx, ny, nz) grid of `cell` at lo, cell_start (nx*ny*nz + 1).
+ */
+int surf_dtu_sample_count(const double* vertices, const int64_t* triangles, int64_t n_tri, double thresh, int64_t* counts,
+                          void* stream);
+int surf_dtu_sample_write(const double* vertices, const int64_t* triangles, int64_t n_tri, double thresh, const int64_t* offsets,
+                          double* out, void* stream);
+int surf_dtu_cell_keys(const double* points, int64_t n, double lo_x, double lo_y, double lo_z, double cell, int64_t nx, int64_t ny,
+                       int64_t nz, int64_t* keys, void* stream);
+int surf_dtu_thin_round(const double* sorted_points, const int32_t* sorted_index, const int32_t* sorted_cell, const int64_t* cell_keys,
+                        const int32_t* cell_start, int64_t n, int64_t n_cells, double thresh, int32_t* state, int32_t* undecided,
+                        void* stream);
+int surf_dtu_nearest(const double* queries, int64_t m, const double* sorted_ref, const int32_t* cell_start, double lo_x, double lo_y,
+                     double lo_z, double cell, int64_t nx, int64_t ny, int64_t nz, double max_dist, double* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -60,6 +60,8 @@ def parse_args(argv=None):
     ap.add_argument("--patch_size", type=float, default=60)
     ap.add_argument("--max_dist", type=float, default=20)
     ap.add_argument("--shuffle_seed", type=int, default=0, help="seed of the thinning shuffle of the evaluator (the reference's is unseeded)")
+    ap.add_argument("--eval_device", default="cpu", choices=["cpu", "gpu"],
+                    help="where the DTU evaluator samples, thins and measures (gpu: the HIP kernels, same numbers)")
     ap.add_argument("--reference_chamfer", type=float, default=None)
     ap.add_argument("--logit_override", default=None, choices=["sphere"],
                     help="(tests) replace the U-Nets' matching logits by a sphere-concentrated field, as an untrained model needs")
@@ -134,7 +136,7 @@ def run(args):
         t0 = time.perf_counter()
         d2s, s2d, overall = dtu_eval.evaluate_scan(mesh_path, args.eval_dir, args.scan, patch_size=args.patch_size,
                                                    max_dist=args.max_dist, downsample_density=args.downsample_density,
-                                                   rng=np.random.default_rng(args.shuffle_seed))
+                                                   rng=np.random.default_rng(args.shuffle_seed), device=args.eval_device)
         t_eval = time.perf_counter() - t0
         return {"scan": args.scan, "d2s": d2s, "s2d": s2d, "chamfer": overall, "reference_chamfer": args.reference_chamfer,
                 "delta": None if args.reference_chamfer is None else overall - args.reference_chamfer,

@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("SURF_HIP_LIB", os.path.join(_HERE, "libsurf_hip.so"))
 
 # must equal SURF_ABI_VERSION of include/surf_hip.h (tests/test_host_modules.py compares the two texts); lib() refuses a
 # library built from another header
-ABI_VERSION = 40
+ABI_VERSION = 41
 
 c_f32p = ctypes.c_void_p
 c_ptr = ctypes.c_void_p
@@ -93,6 +93,11 @@ SIGNATURES = {
     "surf_band_rank": (c_int, [c_ptr, c_i64, c_ptr, c_int, c_ptr, c_ptr]),
     "surf_band_emit": (c_int, [c_ptr, c_ptr, c_int, ctypes.c_double, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     "surf_raster_first_hit": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
+    "surf_dtu_sample_count": (c_int, [c_ptr, c_ptr, c_i64, ctypes.c_double, c_ptr, c_ptr]),
+    "surf_dtu_sample_write": (c_int, [c_ptr, c_ptr, c_i64, ctypes.c_double, c_ptr, c_ptr, c_ptr]),
+    "surf_dtu_cell_keys": (c_int, [c_ptr, c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i64, c_i64, c_i64, c_ptr, c_ptr]),
+    "surf_dtu_thin_round": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, ctypes.c_double, c_ptr, c_ptr, c_ptr]),
+    "surf_dtu_nearest": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i64, c_i64, c_i64, ctypes.c_double, c_ptr, c_ptr]),
     "surf_composite": (c_int, [c_ptr] * 9 + [c_int, c_int, c_float, c_float] + [c_ptr] * 13),
     "surf_upsample_bilinear_t4": (c_int, [c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
     "surf_surface_points": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),

@@ -1,0 +1,274 @@
+// DTU Chamfer evaluation on the device (surf_amd/evaluation/dtu_eval.py, device="gpu"): mesh sampling, greedy thinning and
+// the capped nearest-neighbour distance, each bit-identical to the numpy / scikit-learn path it replaces.
+//
+// All coordinate arithmetic is fp64 in numpy's operation order, and the library is compiled with -ffp-contract=off: no FMA
+// feeds a comparison, a floor or an output coordinate.
+//  * sampling (sample_mesh_points): a count pass and a write pass per triangle; the host scans the counts.  A triangle's
+//    lattice points run i-major, j-minor, so the output equals the CPU array element for element.
+//  * thinning (downsample_points): the greedy pass keeps a sample iff no EARLIER KEPT sample lies within thresh, i.e. the
+//    lexicographically-first maximal independent set.  It is computed in rounds: an undecided sample is removed as soon as
+//    an earlier neighbour is kept, and kept once every earlier neighbour is removed.  States change once (undecided ->
+//    kept / removed), so a stale read only delays a decision and in-place updates are safe; the host repeats rounds until
+//    none is undecided.  Neighbours come from a grid of cells >= thresh (27 cells cover the radius) whose sorted keys are
+//    searched per (x, y) column.  The test is scikit-learn's: (dx*dx + dy*dy) + dz*dz <= thresh*thresh.
+//  * nearest neighbour (NearestNeighbors.kneighbors, capped): shells of a dense cell table around the query's cell, until
+//    the best squared distance is within the shell radius or the shell radius reaches max_dist; +inf when nothing is
+//    nearer than max_dist.  The minimum of the same fp64 squared distances, then one sqrt: scikit-learn's kd-tree value.
+// Offline evaluation: gather bound, not part of the training / render hot path.
+#include <math.h>
+
+#include "common.h"
+
+namespace {
+
+constexpr int kUndecided = 0, kKept = 1, kRemoved = 2;
+constexpr int64_t kThinAxis = int64_t(1) << 21;   // cells per axis of the thinning grid: keys (x << 42) | (y << 21) | z
+
+struct Tri {
+  double o[3], v1[3], v2[3];
+  int64_t n1, n2;
+  bool ok;
+};
+
+// sample_mesh_points' per-triangle quantities, in numpy's order: np.linalg.norm = sqrt((x*x + y*y) + z*z), np.cross component
+// by component, thr = thresh * sqrt(l1 * l2 / area2), n = floor(l / thr)
+__device__ Tri load_tri(const double* __restrict__ V, const int64_t* __restrict__ T, int64_t t, double thresh) {
+  Tri r;
+  const int64_t a = T[t * 3 + 0], b = T[t * 3 + 1], c = T[t * 3 + 2];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    r.o[k] = V[a * 3 + k];
+    r.v1[k] = V[b * 3 + k] - r.o[k];
+    r.v2[k] = V[c * 3 + k] - r.o[k];
+  }
+  const double l1 = sqrt((r.v1[0] * r.v1[0] + r.v1[1] * r.v1[1]) + r.v1[2] * r.v1[2]);
+  const double l2 = sqrt((r.v2[0] * r.v2[0] + r.v2[1] * r.v2[1]) + r.v2[2] * r.v2[2]);
+  const double c0 = r.v1[1] * r.v2[2] - r.v1[2] * r.v2[1];
+  const double c1 = r.v1[2] * r.v2[0] - r.v1[0] * r.v2[2];
+  const double c2 = r.v1[0] * r.v2[1] - r.v1[1] * r.v2[0];
+  const double area2 = sqrt((c0 * c0 + c1 * c1) + c2 * c2);
+  r.ok = area2 > 0.0;
+  r.n1 = r.n2 = 0;
+  if (r.ok) {
+    const double thr = thresh * sqrt(l1 * l2 / area2);
+    r.n1 = (int64_t)floor(l1 / thr);
+    r.n2 = (int64_t)floor(l2 / thr);
+  }
+  return r;
+}
+
+// (i + 0.5) / max(n, 1e-7) as numpy computes it on the float64 mgrid
+__device__ __forceinline__ double lattice(int64_t i, int64_t n) {
+  return ((double)i + 0.5) / (n > 0 ? (double)n : 1e-7);
+}
+
+__global__ __launch_bounds__(256) void sample_count_kernel(const double* __restrict__ V, const int64_t* __restrict__ T, int64_t nt,
+                                                           double thresh, int64_t* __restrict__ counts) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nt) return;
+  const Tri r = load_tri(V, T, t, thresh);
+  int64_t cnt = 0;
+  if (r.ok)
+    for (int64_t i = 0; i <= r.n1; ++i) {
+      const double ci = lattice(i, r.n1);
+      for (int64_t j = 0; j <= r.n2 && ci + lattice(j, r.n2) < 1.0; ++j) ++cnt;   // ci + cj grows with j
+    }
+  counts[t] = cnt;
+}
+
+__global__ __launch_bounds__(256) void sample_write_kernel(const double* __restrict__ V, const int64_t* __restrict__ T, int64_t nt,
+                                                           double thresh, const int64_t* __restrict__ offsets, double* __restrict__ out) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nt) return;
+  const Tri r = load_tri(V, T, t, thresh);
+  if (!r.ok) return;
+  double* o = out + offsets[t] * 3;
+  for (int64_t i = 0; i <= r.n1; ++i) {
+    const double ci = lattice(i, r.n1);
+    for (int64_t j = 0; j <= r.n2; ++j) {
+      const double cj = lattice(j, r.n2);
+      if (!(ci + cj < 1.0)) break;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) o[k] = (r.v1[k] * ci + r.v2[k] * cj) + r.o[k];
+      o += 3;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void cell_keys_kernel(const double* __restrict__ P, int64_t n, double lx, double ly, double lz,
+                                                        double cell, int64_t nx, int64_t ny, int64_t nz, int64_t* __restrict__ keys) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t cx = min(max((int64_t)floor((P[i * 3 + 0] - lx) / cell), (int64_t)0), nx - 1);
+  const int64_t cy = min(max((int64_t)floor((P[i * 3 + 1] - ly) / cell), (int64_t)0), ny - 1);
+  const int64_t cz = min(max((int64_t)floor((P[i * 3 + 2] - lz) / cell), (int64_t)0), nz - 1);
+  keys[i] = (cx * ny + cy) * nz + cz;
+}
+
+__device__ __forceinline__ int64_t lower_bound(const int64_t* __restrict__ a, int64_t n, int64_t key) {
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (a[mid] < key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ int load_state(const int32_t* s) { return __hip_atomic_load(s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void store_state(int32_t* s, int v) { __hip_atomic_store(s, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+struct ThinArgs {
+  const double* spts;      // (n, 3) samples in cell order
+  const int32_t* sidx;     // (n) their index in the shuffled order (ascending inside a cell)
+  const int32_t* scell;    // (n) their cell's position in ucell
+  const int64_t* ucell;    // (ncell) sorted distinct cell keys
+  const int32_t* cstart;   // (ncell + 1) first sample of each cell
+  int64_t n, ncell;
+  double thresh2;
+  int32_t* state;          // (n) by shuffled index
+  int32_t* undecided;      // (1) incremented by every sample still undecided after its visit
+};
+
+// one round over the samples in cell order (neighbouring threads read neighbouring cells)
+__global__ __launch_bounds__(256) void thin_round_kernel(ThinArgs a) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= a.n) return;
+  const int32_t i = a.sidx[t];
+  if (load_state(&a.state[i]) != kUndecided) return;
+  const double px = a.spts[t * 3 + 0], py = a.spts[t * 3 + 1], pz = a.spts[t * 3 + 2];
+  const int64_t key = a.ucell[a.scell[t]];
+  const int64_t cx = key >> 42, cy = (key >> 21) & (kThinAxis - 1), cz = key & (kThinAxis - 1);
+  bool pending = false;
+  for (int64_t x = max(cx - 1, (int64_t)0); x <= min(cx + 1, kThinAxis - 1); ++x)
+    for (int64_t y = max(cy - 1, (int64_t)0); y <= min(cy + 1, kThinAxis - 1); ++y) {
+      const int64_t col = (x << 42) | (y << 21);
+      const int64_t kend = col | min(cz + 1, kThinAxis - 1);
+      for (int64_t c = lower_bound(a.ucell, a.ncell, col | max(cz - 1, (int64_t)0)); c < a.ncell && a.ucell[c] <= kend; ++c) {
+        const int32_t e = a.cstart[c + 1];
+        for (int32_t s = a.cstart[c]; s < e; ++s) {
+          const int32_t j = a.sidx[s];
+          if (j >= i) break;                 // only earlier samples decide; a cell lists them in shuffled order
+          const double dx = a.spts[(int64_t)s * 3 + 0] - px, dy = a.spts[(int64_t)s * 3 + 1] - py, dz = a.spts[(int64_t)s * 3 + 2] - pz;
+          if ((dx * dx + dy * dy) + dz * dz > a.thresh2) continue;
+          const int st = load_state(&a.state[j]);
+          if (st == kKept) {
+            store_state(&a.state[i], kRemoved);
+            return;
+          }
+          pending |= st == kUndecided;
+        }
+      }
+    }
+  if (pending) atomicAdd(a.undecided, 1);
+  else store_state(&a.state[i], kKept);
+}
+
+struct NearestArgs {
+  const double* q;         // (m, 3) queries
+  int64_t m;
+  const double* ref;       // (r, 3) reference points in cell order
+  const int32_t* cstart;   // (nx*ny*nz + 1) first point of every cell
+  double lo[3], cell, max_dist;
+  int64_t nc[3];
+  double* out;             // (m) distance, +inf where >= max_dist
+};
+
+__global__ __launch_bounds__(256) void nearest_kernel(NearestArgs a) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= a.m) return;
+  const double p[3] = {a.q[t * 3 + 0], a.q[t * 3 + 1], a.q[t * 3 + 2]};
+  // shells beyond kmax lie farther than max_dist (with a margin for the rounding of the cell coordinates)
+  const int64_t kmax = (int64_t)ceil(a.max_dist / (a.cell * (1.0 - 1e-6))) + 1;
+  int64_t c[3];
+  int64_t gap = 0;                           // Chebyshev distance in cells from the query's cell to the grid
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double f = floor((p[k] - a.lo[k]) / a.cell);
+    const double g = f < 0.0 ? -f : f - (double)(a.nc[k] - 1);
+    if (!(g <= (double)kmax)) {              // far outside (or NaN): nothing within max_dist
+      a.out[t] = INFINITY;
+      return;
+    }
+    c[k] = (int64_t)f;
+    gap = max(gap, (int64_t)max(g, 0.0));
+  }
+  const int64_t zlo = 0, zhi = a.nc[2] - 1;
+  double best = INFINITY;
+  for (int64_t k = gap; k <= kmax; ++k) {
+    // shells 0 .. k-1 are visited (those below `gap` miss the grid): every other point lies more than k-1 cells away.  Stop
+    // once the best is within that reach, or the reach is max_dist.
+    const double reach = (double)(k > 0 ? k - 1 : 0) * a.cell * (1.0 - 1e-6);
+    if (best <= reach * reach || reach >= a.max_dist) break;
+    const int64_t x0 = max(c[0] - k, (int64_t)0), x1 = min(c[0] + k, a.nc[0] - 1);
+    const int64_t y0 = max(c[1] - k, (int64_t)0), y1 = min(c[1] + k, a.nc[1] - 1);
+    for (int64_t x = x0; x <= x1; ++x)
+      for (int64_t y = y0; y <= y1; ++y) {
+        // on the rim of the shell's x-y square the whole z column belongs to the shell, inside it only the two z faces
+        const bool rim = x == c[0] - k || x == c[0] + k || y == c[1] - k || y == c[1] + k;
+        const int64_t z0 = rim ? max(c[2] - k, zlo) : c[2] - k, z1 = rim ? min(c[2] + k, zhi) : c[2] + k;
+        for (int64_t z = z0; z <= z1; z += rim ? 1 : 2 * k) {
+          if (z < zlo || z > zhi) continue;
+          const int64_t cell = (x * a.nc[1] + y) * a.nc[2] + z;
+          const int32_t e = a.cstart[cell + 1];
+          for (int32_t s = a.cstart[cell]; s < e; ++s) {
+            const double dx = p[0] - a.ref[(int64_t)s * 3 + 0], dy = p[1] - a.ref[(int64_t)s * 3 + 1], dz = p[2] - a.ref[(int64_t)s * 3 + 2];
+            best = fmin(best, (dx * dx + dy * dy) + dz * dz);
+          }
+        }
+      }
+  }
+  const double d = sqrt(best);
+  a.out[t] = d < a.max_dist ? d : INFINITY;
+}
+
+inline unsigned blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+}  // namespace
+
+extern "C" int surf_dtu_sample_count(const double* vertices, const int64_t* triangles, int64_t n_tri, double thresh, int64_t* counts,
+                                     void* stream) {
+  if (!vertices || !triangles || !counts || n_tri <= 0 || !(thresh > 0.0)) return SURF_E_ARG;
+  hipLaunchKernelGGL(sample_count_kernel, dim3(blocks(n_tri)), dim3(256), 0, (hipStream_t)stream, vertices, triangles, n_tri, thresh,
+                     counts);
+  return surf_check_launch();
+}
+
+extern "C" int surf_dtu_sample_write(const double* vertices, const int64_t* triangles, int64_t n_tri, double thresh,
+                                     const int64_t* offsets, double* out, void* stream) {
+  if (!vertices || !triangles || !offsets || !out || n_tri <= 0 || !(thresh > 0.0)) return SURF_E_ARG;
+  hipLaunchKernelGGL(sample_write_kernel, dim3(blocks(n_tri)), dim3(256), 0, (hipStream_t)stream, vertices, triangles, n_tri, thresh,
+                     offsets, out);
+  return surf_check_launch();
+}
+
+extern "C" int surf_dtu_cell_keys(const double* points, int64_t n, double lo_x, double lo_y, double lo_z, double cell, int64_t nx,
+                                  int64_t ny, int64_t nz, int64_t* keys, void* stream) {
+  if (!points || !keys || n <= 0 || !(cell > 0.0) || nx <= 0 || ny <= 0 || nz <= 0) return SURF_E_ARG;
+  if (nx > kThinAxis || ny > kThinAxis || nz > kThinAxis) return SURF_E_LIMIT;
+  hipLaunchKernelGGL(cell_keys_kernel, dim3(blocks(n)), dim3(256), 0, (hipStream_t)stream, points, n, lo_x, lo_y, lo_z, cell, nx, ny,
+                     nz, keys);
+  return surf_check_launch();
+}
+
+extern "C" int surf_dtu_thin_round(const double* sorted_points, const int32_t* sorted_index, const int32_t* sorted_cell,
+                                   const int64_t* cell_keys, const int32_t* cell_start, int64_t n, int64_t n_cells, double thresh,
+                                   int32_t* state, int32_t* undecided, void* stream) {
+  if (!sorted_points || !sorted_index || !sorted_cell || !cell_keys || !cell_start || !state || !undecided) return SURF_E_ARG;
+  if (n <= 0 || n_cells <= 0 || n_cells > n || !(thresh >= 0.0)) return SURF_E_ARG;
+  if (n > INT32_MAX) return SURF_E_LIMIT;
+  hipError_t e = hipMemsetAsync(undecided, 0, sizeof(int32_t), (hipStream_t)stream);
+  if (e != hipSuccess) return (int)e;
+  ThinArgs a{sorted_points, sorted_index, sorted_cell, cell_keys, cell_start, n, n_cells, thresh * thresh, state, undecided};
+  hipLaunchKernelGGL(thin_round_kernel, dim3(blocks(n)), dim3(256), 0, (hipStream_t)stream, a);
+  return surf_check_launch();
+}
+
+extern "C" int surf_dtu_nearest(const double* queries, int64_t m, const double* sorted_ref, const int32_t* cell_start, double lo_x,
+                                double lo_y, double lo_z, double cell, int64_t nx, int64_t ny, int64_t nz, double max_dist, double* out,
+                                void* stream) {
+  if (!queries || !sorted_ref || !cell_start || !out || m <= 0 || !(cell > 0.0) || !(max_dist > 0.0)) return SURF_E_ARG;
+  if (nx <= 0 || ny <= 0 || nz <= 0 || nx > kThinAxis || ny > kThinAxis || nz > kThinAxis) return SURF_E_ARG;
+  NearestArgs a{queries, m, sorted_ref, cell_start, {lo_x, lo_y, lo_z}, cell, max_dist, {nx, ny, nz}, out};
+  hipLaunchKernelGGL(nearest_kernel, dim3(blocks(m)), dim3(256), 0, (hipStream_t)stream, a);
+  return surf_check_launch();
+}

@@ -1315,6 +1315,123 @@ def raster_first_hit(vertices, faces, intr, c2w, hw, upscale=1):
     return torch.where(zbuf == -1, torch.full_like(zbuf, -1), zbuf & 0xffffffff)
 
 
+# ------------------------------------------------------------------------------------------------
+# DTU Chamfer evaluation (dtu_eval.hip): mesh sampling, greedy thinning, capped nearest neighbour, all fp64
+# ------------------------------------------------------------------------------------------------
+
+THIN_AXIS_CELLS = 1 << 21        # cells per axis of a dtu_eval grid (63-bit keys)
+NEAREST_MAX_CELLS = 1 << 26      # dense cell table of nearest_dist_capped
+
+
+def _box(points):
+    """Per-axis min and extent of a (n, 3) device tensor, on the host (one sync)."""
+    lo, hi = points.amin(0).tolist(), points.amax(0).tolist()
+    return lo, [b - a for a, b in zip(lo, hi)]
+
+
+def mesh_sample_points(vertices, triangles, thresh):
+    """dtu_eval.sample_mesh_points on the device: (nv + samples, 3) float64, the vertices followed by the lattice samples of
+    every triangle of non-zero area, triangle by triangle.  vertices (nv, 3) float64, triangles (nt, 3) int64.  One host
+    sync sizes the output (plus one that checks the triangle indices)."""
+    _chk(vertices, torch.float64, "vertices")
+    _chk(triangles, torch.int64, "triangles")
+    nv, nt = vertices.shape[0], triangles.shape[0]
+    if nt == 0:
+        return vertices.clone()
+    lo, hi = (int(v) for v in torch.stack([triangles.min(), triangles.max()]).tolist())
+    if lo < 0 or hi >= nv:
+        raise IndexError(f"triangles index vertices {lo}..{hi} of {nv}")
+    L = _lib.lib()
+    counts = torch.empty(nt, dtype=torch.int64, device=vertices.device)
+    _lib.check(L.surf_dtu_sample_count(_p(vertices), _p(triangles), nt, float(thresh), _p(counts), _stream()), "surf_dtu_sample_count")
+    ends = torch.cumsum(counts, 0)
+    total = int(ends[-1])
+    out = torch.empty(nv + total, 3, dtype=torch.float64, device=vertices.device)
+    out[:nv] = vertices
+    if total:
+        _lib.check(L.surf_dtu_sample_write(_p(vertices), _p(triangles), nt, float(thresh), _p(ends - counts), _p(out[nv:]), _stream()),
+                   "surf_dtu_sample_write")
+    return out
+
+
+def thin_points(points, thresh, max_rounds=10000):
+    """Greedy thinning of dtu_eval.downsample_points on already shuffled points (n, 3) float64: keep a point iff no earlier
+    KEPT point lies within `thresh` ((dx*dx + dy*dy) + dz*dz <= thresh*thresh, scikit-learn's radius_neighbors test).
+    Returns (keep (n,) bool, rounds): the parallel rounds it took, each ending in one host sync."""
+    _chk(points, torch.float64, "points")
+    n = points.shape[0]
+    dev = points.device
+    if n == 0:
+        return torch.zeros(0, dtype=torch.bool, device=dev), 0
+    if n > 2 ** 31 - 1:
+        raise ValueError(f"thin_points: {n} points exceed int32 indexing")
+    L = _lib.lib()
+    lo, ext = _box(points)
+    # cells a little wider than thresh (so that rounding in floor((p - lo) / cell) cannot push a neighbour two cells away),
+    # wider still if an axis would need more than THIN_AXIS_CELLS
+    cell = max(float(thresh) * (1 + 1e-6), max(ext) / (THIN_AXIS_CELLS - 2) * (1 + 1e-6))
+    if not cell > 0:
+        cell = 1.0
+    A = THIN_AXIS_CELLS
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    _lib.check(L.surf_dtu_cell_keys(_p(points), n, lo[0], lo[1], lo[2], cell, A, A, A, _p(keys), _stream()), "surf_dtu_cell_keys")
+    skeys, order = torch.sort(keys, stable=True)              # stable: a cell lists its points in shuffled order
+    ucell, scell, counts = torch.unique_consecutive(skeys, return_inverse=True, return_counts=True)
+    cstart = torch.zeros(ucell.shape[0] + 1, dtype=torch.int32, device=dev)
+    cstart[1:] = torch.cumsum(counts, 0)
+    spts = points[order].contiguous()
+    sidx = order.to(torch.int32)
+    scell = scell.to(torch.int32)
+    state = torch.zeros(n, dtype=torch.int32, device=dev)
+    undecided = torch.empty(1, dtype=torch.int32, device=dev)
+    rounds = 0
+    while True:
+        _lib.check(L.surf_dtu_thin_round(_p(spts), _p(sidx), _p(scell), _p(ucell), _p(cstart), n, ucell.shape[0], float(thresh),
+                                         _p(state), _p(undecided), _stream()), "surf_dtu_thin_round")
+        rounds += 1
+        if int(undecided.item()) == 0:
+            break
+        if rounds >= max_rounds:
+            raise RuntimeError(f"thin_points: {int(undecided.item())} of {n} points still undecided after {rounds} rounds")
+    return state == 1, rounds
+
+
+def nearest_dist_capped(queries, ref, max_dist):
+    """Distance from every query (m, 3) float64 to its nearest reference point (r, 3) float64 where that is < max_dist, +inf
+    elsewhere (scikit-learn's kneighbors(n_neighbors=1) distance, bit for bit).  Two host syncs (the reference box)."""
+    _chk(queries, torch.float64, "queries")
+    _chk(ref, torch.float64, "ref")
+    m, r = queries.shape[0], ref.shape[0]
+    dev = queries.device
+    if not (max_dist > 0 and np.isfinite(max_dist)):
+        raise ValueError(f"nearest_dist_capped: max_dist must be finite and > 0, got {max_dist}")
+    if m == 0 or r == 0:
+        return torch.full((m,), float("inf"), dtype=torch.float64, device=dev)
+    if r > 2 ** 31 - 1:
+        raise ValueError(f"nearest_dist_capped: {r} reference points exceed int32 indexing")
+    L = _lib.lib()
+    lo, ext = _box(ref)
+    pad = max(ext) * 1e-3 or 1.0                  # flat or single-point clouds still get a box of some volume
+    vol = (ext[0] + pad) * (ext[1] + pad) * (ext[2] + pad)
+    cell = max((vol / (4.0 * r)) ** (1.0 / 3.0), max(ext) / (THIN_AXIS_CELLS - 2))   # about four cells per reference point
+    while True:
+        dims = [int(e // cell) + 1 for e in ext]
+        if dims[0] * dims[1] * dims[2] <= NEAREST_MAX_CELLS:
+            break
+        cell *= 1.25
+    keys = torch.empty(r, dtype=torch.int64, device=dev)
+    _lib.check(L.surf_dtu_cell_keys(_p(ref), r, lo[0], lo[1], lo[2], cell, dims[0], dims[1], dims[2], _p(keys), _stream()),
+               "surf_dtu_cell_keys")
+    skeys, order = torch.sort(keys)
+    cstart = torch.zeros(dims[0] * dims[1] * dims[2] + 1, dtype=torch.int32, device=dev)
+    cstart[1:] = torch.cumsum(torch.bincount(skeys, minlength=dims[0] * dims[1] * dims[2]), 0)
+    sref = ref[order].contiguous()
+    out = torch.empty(m, dtype=torch.float64, device=dev)
+    _lib.check(L.surf_dtu_nearest(_p(queries), m, _p(sref), _p(cstart), lo[0], lo[1], lo[2], cell, dims[0], dims[1], dims[2],
+                                  float(max_dist), _p(out), _stream()), "surf_dtu_nearest")
+    return out
+
+
 def marching_cubes(u, isovalue=0.0):
     """mcubes.marching_cubes(u, isovalue) (implicit_surface.py:353) on a device lattice u (nx, ny, nz) fp32.
     Returns (vertices (nv, 3) float64, triangles (nt, 3) int32) device tensors, vertices in lattice-index units.
