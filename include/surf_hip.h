@@ -741,6 +741,48 @@ int surf_dtu_thin_round(const double* sorted_points, const int32_t* sorted_index
 int surf_dtu_nearest(const double* queries, int64_t m, const double* sorted_ref, const int32_t* cell_start, double lo_x, double lo_y,
                      double lo_z, double cell, int64_t nx, int64_t ny, int64_t nz, double max_dist, double* out, void* stream);
 
+/*
+ * Mesh cleaning on the device (surf_amd/evaluation/clean_mesh.py, backend="device"; mesh_clean.hip).  Every stage returns what
+ * the host stage returns.  These entry points were ADDED under SURF_ABI_VERSION 41 without a bump: the rule above is about
+ * signatures that change, none did, and a library that lacks one of them is refused by name (surf_amd/_lib.py lib()).
+ * Faces are (n,3) int32, masks uint8 (0 = unset), flags / keep arrays uint8, all on the device.  n_faces or n_vertices >= 2^31,
+ * or a component table beyond 2^31 slots, is SURF_E_LIMIT.
+ *   surf_clean_dilate: out = binary dilation of masks (n_views,h,w) with the disk dx*dx + dy*dy <= radius^2, outside unset.
+ *   surf_clean_hull_count: n_seen[v] = number of views that see vertex v: in front of the camera, inside the image, and on a
+ *     set texel of the view's mask under the four-texel bilinear footprint.  vertices (n,3) fp32; cams (n_views,21) fp32 on
+ *     the DEVICE: K row-major (9) then inverse(c2w)[:3,:4] row-major (12).  The fp32 operation order is fixed and written out
+ *     in mesh_clean.hip's header comment.
+ *   surf_clean_face_keep: keep[f] = n_seen > min_nb_visible for the three vertices of f.
+ *   surf_clean_mark_visible: seen[face] = 1 for every sample of surf_raster_first_hit's zbuf (Hup = h*upscale, Wup = w*upscale)
+ *     that holds a hit and whose texel (i / upscale, j / upscale) of mask (h,w) is set; seen (n_faces) is not cleared.
+ *   surf_clean_components: keep[f] = f shares an undirected edge with a face AND its edge-connected component has >= min_len
+ *     faces (trimesh.graph.connected_components on face_adjacency; an edge of k faces joins all k).  Lock-free union-find over
+ *     an edge hash table.  Work arrays, contents ignored: keys (slots) uint64, owner (slots) int32, shared (slots) uint8,
+ *     edge_slot (3 n_faces) uint32, parent / size (n_faces) int32, has_nb (n_faces) uint8; slots = surf_clean_components_slots
+ *     (n_faces) (< 0: SURF_E_*).  On return parent[f] is the smallest face id of f's component, size[parent[f]] its face count.
+ *   surf_clean_mark_used: used[v] = 1 for the vertices of the faces with keep != 0 (used is not cleared).
+ *   surf_clean_compact_faces: out[face_scan[f] - 1] = vertex_scan[faces[f]] - 1 for the kept faces (vertex_scan NULL: the ids
+ *     unchanged); the scans are INCLUSIVE int64 prefix sums of keep and used.
+ *   surf_clean_compact_rows: out[scan[i] - 1] = src[i] for rows of three elem_bytes (4 or 8) elements with flags[i] != 0.
+ */
+int surf_clean_dilate(const uint8_t* masks, int n_views, int h, int w, int radius, uint8_t* out, void* stream);
+int surf_clean_hull_count(const float* vertices, int64_t n_vertices, const uint8_t* masks, const float* cams, int n_views, int h,
+                          int w, int32_t* n_seen, void* stream);
+int surf_clean_face_keep(const int32_t* n_seen, const int32_t* faces, int64_t n_faces, int min_nb_visible, uint8_t* keep,
+                         void* stream);
+int surf_clean_mark_visible(const unsigned long long* zbuf, int Hup, int Wup, const uint8_t* mask, int h, int w, int upscale,
+                            int64_t n_faces, uint8_t* seen, void* stream);
+int64_t surf_clean_components_slots(int64_t n_faces);
+int surf_clean_components(const int32_t* faces, int64_t n_faces, int64_t min_len, unsigned long long* keys, int32_t* owner,
+                          uint8_t* shared, int64_t slots, uint32_t* edge_slot, int32_t* parent, uint8_t* has_nb, int32_t* size,
+                          uint8_t* keep, void* stream);
+int surf_clean_mark_used(const int32_t* faces, const uint8_t* keep, int64_t n_faces, int64_t n_vertices, uint8_t* used,
+                         void* stream);
+int surf_clean_compact_faces(const int32_t* faces, const uint8_t* keep, const int64_t* face_scan, const int64_t* vertex_scan,
+                             int64_t n_faces, int64_t n_vertices, int32_t* out, void* stream);
+int surf_clean_compact_rows(const void* src, int elem_bytes, const uint8_t* flags, const int64_t* scan, int64_t n, void* out,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,8 @@
 
 loader (surf_amd.datasets, the val_dataset block of the HOCON conf)  ->  SuRF(conf.model).load_state_dict(ckpt["model"])
 -> model("val", inputs)                                     (runner.py:213-229: FPN, 4-stage volumes, render, SDF lattice, marching cubes)
--> [clean_mesh with the item's masks, --clean_mesh]         (runner.py:233-234, utils/clean_mesh.py:110-130)
+-> [clean_mesh with the item's masks, --clean_mesh]         (runner.py:233-234, utils/clean_mesh.py:110-130;
+                                                             --clean_backend device: the same cleaned mesh from mesh_clean.hip)
 -> mesh_io.export_mesh(<out>/meshes/final/scan<N>.ply, scale_mat)   (runner.py:236-240; the file name evaluation/dtu_eval.py reads)
 -> evaluation.dtu_eval.evaluate_scan                        (evaluation/dtu_eval.py:31-190)
 -> one JSON line: {"scan", "d2s", "s2d", "chamfer", "reference_chamfer", "delta", ...}.
@@ -56,6 +57,8 @@ def parse_args(argv=None):
     ap.add_argument("--mesh_extraction", default=None, choices=["dense", "band"],
                     help="model.implicit_surface.render.mesh_extraction: whole lattice or bricks near the surface (same mesh)")
     ap.add_argument("--clean_mesh", action="store_true", help="runner.py --clean_mesh: drop faces outside the dilated masks / frusta")
+    ap.add_argument("--clean_backend", default="host", choices=["host", "device"],
+                    help="where --clean_mesh runs (device: the HIP kernels of mesh_clean.hip, same cleaned mesh)")
     ap.add_argument("--downsample_density", type=float, default=0.2)
     ap.add_argument("--patch_size", type=float, default=60)
     ap.add_argument("--max_dist", type=float, default=20)
@@ -128,8 +131,10 @@ def run(args):
             if tag:                      # a sweep candidate that scrambles the checkpoint may well produce no surface at all
                 return {"scan": args.scan, "chamfer": None, "error": "empty mesh", **conv}
             raise SystemExit("dtu_chamfer: the SDF lattice has no zero crossing inside the bounding box (empty mesh)")
+        t0 = time.perf_counter()
         if args.clean_mesh:
-            v, t = CM.clean_mesh(v, t, item["masks"], item["intrs"], item["c2ws"], device=dev.type)
+            v, t = CM.clean_mesh(v, t, item["masks"], item["intrs"], item["c2ws"], device=dev.type, backend=args.clean_backend)
+        t_clean = time.perf_counter() - t0
         mesh_path = os.path.join(args.out_dir, "meshes", "final" + tag, f"scan{args.scan}.ply")
         os.makedirs(os.path.dirname(mesh_path), exist_ok=True)
         mesh_io.export_mesh(mesh_path, v, t, item["scale_mat"])                                   # runner.py:236-240
@@ -144,7 +149,8 @@ def run(args):
                 "views": int(item["imgs"].shape[0]), "render_hw": [int(x) for x in out["img_fine"].shape[:2]],
                 **conv, "sdf_precision": model.implicit_surface.sdf_precision,
                 "checkpoint": args.ckpt, "missing_keys": missing, "unexpected_keys": unexpected, "cleaned": bool(args.clean_mesh),
-                "seconds": {"load": t_load, "val_forward": t_val, "evaluate": t_eval}}
+                "clean_backend": args.clean_backend if args.clean_mesh else None,
+                "seconds": {"load": t_load, "val_forward": t_val, "clean": t_clean, "evaluate": t_eval}}
 
     if not args.sweep:
         rec = evaluate()

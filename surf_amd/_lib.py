@@ -98,6 +98,15 @@ SIGNATURES = {
     "surf_dtu_cell_keys": (c_int, [c_ptr, c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i64, c_i64, c_i64, c_ptr, c_ptr]),
     "surf_dtu_thin_round": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, ctypes.c_double, c_ptr, c_ptr, c_ptr]),
     "surf_dtu_nearest": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i64, c_i64, c_i64, ctypes.c_double, c_ptr, c_ptr]),
+    "surf_clean_dilate": (c_int, [c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
+    "surf_clean_hull_count": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr]),
+    "surf_clean_face_keep": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr]),
+    "surf_clean_mark_visible": (c_int, [c_ptr, c_int, c_int, c_ptr, c_int, c_int, c_int, c_i64, c_ptr, c_ptr]),
+    "surf_clean_components_slots": (c_i64, [c_i64]),
+    "surf_clean_components": (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "surf_clean_mark_used": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
+    "surf_clean_compact_faces": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
+    "surf_clean_compact_rows": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
     "surf_composite": (c_int, [c_ptr] * 9 + [c_int, c_int, c_float, c_float] + [c_ptr] * 13),
     "surf_upsample_bilinear_t4": (c_int, [c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
     "surf_surface_points": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),

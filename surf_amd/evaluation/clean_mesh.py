@@ -10,7 +10,11 @@ trimesh / pyembree / skimage / open3d are not dependencies: the first-hit test r
 scipy.sparse.csgraph.  Meshes are (vertices (V,3) float, faces (F,3) int) arrays.
 One deviation, on purpose: the reference drops the smallest hit id assuming it is the "no hit" marker -1
 (`hull_mask[values[1:]] = 1`, utils/clean_mesh.py:96-97), which would discard a real face when every ray hits; here the
-no-hit marker is excluded explicitly."""
+no-hit marker is excluded explicitly.
+
+backend="host" (the default) is the path above.  backend="device" runs every stage on the GPU (csrc/mesh_clean.hip through the
+surf_amd.ops.clean_* wrappers) and returns the same arrays: the *_device functions below are the stage-by-stage twins.  They
+take numpy arrays or device tensors and return device tensors; only clean_mesh converts back (unless return_tensors=True)."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -120,9 +124,125 @@ def clean_mesh_outside_frustum(vertices, faces, masks, intrs, c2ws, upscale=4, m
     return update_faces(vertices, faces, face_components(faces, min_component))
 
 
+# ---- the device path ----
+
+def _dev_mesh(vertices, faces, device):
+    """(vertices in their own dtype, fp32 copy, int32 faces) as contiguous device tensors; one host read validates the face
+    indices (the kernels index the vertex array with them)."""
+    v = vertices if torch.is_tensor(vertices) else torch.from_numpy(np.ascontiguousarray(vertices))
+    f = faces if torch.is_tensor(faces) else torch.from_numpy(np.ascontiguousarray(faces))
+    v = v.to(device).contiguous()
+    if v.dtype not in (torch.float32, torch.float64):
+        v = v.to(torch.float64)
+    f = f.to(device)
+    if f.numel():
+        lo, hi = (int(x) for x in torch.stack([f.min(), f.max()]).tolist())
+        if lo < 0 or hi >= v.shape[0]:
+            raise ValueError(f"face indices span [{lo}, {hi}], the mesh has {v.shape[0]} vertices")
+    return v, v.to(torch.float32).contiguous(), f.to(torch.int32).contiguous().reshape(-1, 3)
+
+
+def _dev_faces(faces, device):
+    f = faces if torch.is_tensor(faces) else torch.from_numpy(np.ascontiguousarray(faces))
+    return f.to(device=device, dtype=torch.int32).contiguous().reshape(-1, 3)
+
+
+def _dev_masks(masks, device):
+    """(nv, h, w) bool / uint8 / float masks -> uint8 device tensor of (mask > 0)."""
+    m = masks if torch.is_tensor(masks) else torch.from_numpy(np.ascontiguousarray(masks))
+    return (m.to(device) > 0).to(torch.uint8).contiguous()
+
+
+def dilate_disk_device(masks, radius, device="cuda"):
+    """dilate_disk of one (h, w) mask or of every slice of (nv, h, w) masks; bool device tensor of the same shape."""
+    from .. import ops
+    m = _dev_masks(masks, device)
+    return ops.clean_dilate(m[None], radius)[0] if m.dim() == 2 else ops.clean_dilate(m, radius)
+
+
+def vertex_seen_count_device(vertices, masks, intrs, c2ws, device="cuda"):
+    """n_seen of clean_mesh_by_mask for every vertex ((V,) int32 device tensor), in the fixed fp32 operation order written in
+    csrc/mesh_clean.hip."""
+    from .. import ops
+    v = vertices if torch.is_tensor(vertices) else torch.from_numpy(np.ascontiguousarray(vertices))
+    return ops.clean_hull_count(v.to(device=device, dtype=torch.float32).contiguous(), _dev_masks(masks, device), intrs, c2ws)
+
+
+def clean_mesh_by_mask_device(vertices, faces, masks, intrs, c2ws, min_nb_visible=1, device="cuda"):
+    """clean_mesh_by_mask on the device: (F,) bool device tensor."""
+    from .. import ops
+    n_seen = vertex_seen_count_device(vertices, masks, intrs, c2ws, device)
+    return ops.clean_face_keep(n_seen, _dev_faces(faces, device), min_nb_visible)
+
+
+def visible_faces_device(vertices, faces, masks, intrs, c2ws, upscale=4, device="cuda"):
+    """visible_faces on the device, without the up-scaled mask and the id image: (F,) bool device tensor."""
+    from .. import ops
+    v = vertices if torch.is_tensor(vertices) else torch.from_numpy(np.ascontiguousarray(vertices))
+    return ops.clean_visible_faces(v.to(device=device, dtype=torch.float32).contiguous(), _dev_faces(faces, device),
+                                   _dev_masks(masks, device), intrs, c2ws, upscale)
+
+
+def face_components_device(faces, min_len, device="cuda"):
+    """face_components on the device (lock-free union-find over an edge hash table): (F,) bool device tensor."""
+    from .. import ops
+    return ops.clean_components(_dev_faces(faces, device), min_len)
+
+
+def update_faces_device(vertices, faces, keep, device="cuda"):
+    """update_faces on the device: (vertices in the dtype they came in, faces int64) device tensors, order preserved."""
+    from .. import ops
+    v = vertices if torch.is_tensor(vertices) else torch.from_numpy(np.ascontiguousarray(vertices))
+    k = keep if torch.is_tensor(keep) else torch.from_numpy(np.ascontiguousarray(keep))
+    v, f = ops.clean_update_faces(v.to(device).contiguous(), _dev_faces(faces, device), k.to(device).to(torch.bool).contiguous())
+    return v, f.long()
+
+
+def clean_mesh_outside_frustum_device(vertices, faces, masks, intrs, c2ws, upscale=4, min_component=500, device="cuda"):
+    """clean_mesh_outside_frustum on the device: (vertices, faces int64) device tensors."""
+    from .. import ops
+    v, v32, f = _dev_mesh(vertices, faces, device)
+    return _outside_frustum_device(ops, v, v32, f, _dev_masks(masks, device), intrs, c2ws, upscale, min_component)
+
+
+def _outside_frustum_device(ops, v, v32, f, masks, intrs, c2ws, upscale, min_component):
+    keep = ops.clean_visible_faces(v32, f, masks, intrs, c2ws, upscale)
+    v, f = ops.clean_update_faces(v, f, keep)
+    v, f = ops.clean_update_faces(v, f, ops.clean_components(f, min_component))
+    return v, f.long()
+
+
+@torch.no_grad()
+def clean_mesh_device(vertices, faces, masks, intrs, c2ws, dilation_radius=11, min_nb_visible=1, upscale=2, min_component=500,
+                      device="cuda", return_tensors=False):
+    """clean_mesh with every stage on the device.  Numpy arrays or tensors in; numpy arrays out, or device tensors with
+    return_tensors=True (no host copy of the mesh then).  Vertices keep the dtype they came in."""
+    from .. import ops
+    if device == "cpu" or not torch.cuda.is_available():
+        raise RuntimeError('clean_mesh(backend="device") needs a GPU: there is no host fall-back for the device path')
+    masks = masks if torch.is_tensor(masks) else torch.from_numpy(np.ascontiguousarray(masks))
+    if masks.dim() > 3:
+        masks = masks.cpu().mean(dim=-1)                   # as the host path computes it: the 0.5 threshold reads this value
+    masks = masks.to(device)
+    v, v32, f = _dev_mesh(vertices, faces, device)
+    dilated = ops.clean_dilate((masks > 0.5).to(torch.uint8).contiguous(), dilation_radius)
+    keep = ops.clean_face_keep(ops.clean_hull_count(v32, dilated, intrs, c2ws), f, min_nb_visible)
+    _, f = ops.clean_update_faces(v, f, keep, compact_vertices=False)         # Trimesh.update_faces keeps the vertex list
+    v, f = _outside_frustum_device(ops, v, v32, f, (masks > 0).to(torch.uint8).contiguous(), intrs, c2ws, upscale, min_component)
+    return (v, f) if return_tensors else (v.cpu().numpy(), f.cpu().numpy())
+
+
 def clean_mesh(vertices, faces, masks, intrs, c2ws, dilation_radius=11, min_nb_visible=1, upscale=2, min_component=500,
-               device="cuda"):
-    """utils/clean_mesh.py:110-130 (the entry runner.py:233-234 calls with --clean_mesh)."""
+               device="cuda", backend="host", return_tensors=False):
+    """utils/clean_mesh.py:110-130 (the entry runner.py:233-234 calls with --clean_mesh).  backend="device": the same result
+    with every stage on the GPU (clean_mesh_device); `device` is the torch device the GPU work runs on in both cases."""
+    if backend == "device":
+        return clean_mesh_device(vertices, faces, masks, intrs, c2ws, dilation_radius, min_nb_visible, upscale, min_component,
+                                 device, return_tensors)
+    if backend != "host":
+        raise ValueError(f"backend: expected 'host' or 'device', got {backend!r}")
+    if return_tensors:
+        raise ValueError('return_tensors=True needs backend="device"')
     intrs, c2ws, masks = intrs.cpu(), c2ws.cpu(), masks.cpu()
     if masks.dim() > 3:
         masks = masks.mean(dim=-1)

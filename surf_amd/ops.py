@@ -1432,6 +1432,154 @@ def nearest_dist_capped(queries, ref, max_dist):
     return out
 
 
+# ------------------------------------------------------------------------------------------------
+# mesh cleaning (mesh_clean.hip): dilation, visual hull, visible faces, face components, compaction
+# ------------------------------------------------------------------------------------------------
+
+
+def _camera_rows(intrs, c2ws, dev):
+    """(nv, 21) fp32 device rows [K row-major | inverse(c2w)[:3, :4] row-major], computed on the host as raster_first_hit
+    computes them."""
+    rows = [torch.cat([K.detach().to("cpu", torch.float32)[:3, :3].reshape(-1),
+                       torch.inverse(c2w.detach().to("cpu", torch.float32))[:3, :4].reshape(-1)])
+            for K, c2w in zip(intrs, c2ws)]
+    return torch.stack(rows).contiguous().to(dev)
+
+
+def clean_dilate(masks, radius):
+    """clean_mesh.dilate_disk of every (h, w) slice of masks (nv, h, w) uint8 / bool on the device; returns bool."""
+    m = masks.view(torch.uint8) if masks.dtype == torch.bool else masks
+    _chk(m, torch.uint8, "masks")
+    assert m.dim() == 3
+    out = torch.empty_like(m)
+    if m.numel():
+        nv, h, w = m.shape
+        _lib.check(_lib.lib().surf_clean_dilate(_p(m), nv, h, w, int(radius), _p(out), _stream()), "surf_clean_dilate")
+    return out.view(torch.bool)
+
+
+def clean_hull_count(vertices, masks, intrs, c2ws):
+    """Per-vertex number of views that see the vertex (clean_mesh.clean_mesh_by_mask's n_seen), int32.  vertices (n, 3) fp32,
+    masks (nv, h, w) uint8 / bool on the device, intrs / c2ws host or device (nv, 4, 4)."""
+    _chk(vertices, torch.float32, "vertices")
+    m = masks.view(torch.uint8) if masks.dtype == torch.bool else masks
+    _chk(m, torch.uint8, "masks")
+    nv, h, w = m.shape
+    n = vertices.shape[0]
+    n_seen = torch.zeros(n, dtype=torch.int32, device=vertices.device)
+    if n == 0 or nv == 0:
+        return n_seen
+    cams = _camera_rows(intrs, c2ws, vertices.device)
+    _lib.check(_lib.lib().surf_clean_hull_count(_p(vertices), n, _p(m), _p(cams), nv, h, w, _p(n_seen), _stream()),
+               "surf_clean_hull_count")
+    return n_seen
+
+
+def clean_face_keep(n_seen, faces, min_nb_visible):
+    """keep (F,) bool: each vertex of the face has n_seen > min_nb_visible."""
+    _chk(n_seen, torch.int32, "n_seen")
+    _chk(faces, torch.int32, "faces")
+    keep = torch.empty(faces.shape[0], dtype=torch.uint8, device=faces.device)
+    if faces.shape[0]:
+        _lib.check(_lib.lib().surf_clean_face_keep(_p(n_seen), _p(faces), faces.shape[0], int(min_nb_visible), _p(keep), _stream()),
+                   "surf_clean_face_keep")
+    return keep.view(torch.bool)
+
+
+def clean_visible_faces(vertices, faces, masks, intrs, c2ws, upscale):
+    """clean_mesh.visible_faces without the up-scaled mask, the id image and the gather: per view, the z-buffer of
+    surf_raster_first_hit and one marking pass.  masks (nv, h, w) uint8 / bool on the device; returns (F,) bool."""
+    _chk(vertices, torch.float32, "vertices")
+    _chk(faces, torch.int32, "faces")
+    m = masks.view(torch.uint8) if masks.dtype == torch.bool else masks
+    _chk(m, torch.uint8, "masks")
+    if int(upscale) != upscale or upscale < 1:
+        raise ValueError("the device cleaner takes an integer upscale >= 1")
+    upscale = int(upscale)
+    nv, h, w = m.shape
+    nf = faces.shape[0]
+    seen = torch.zeros(nf, dtype=torch.uint8, device=faces.device)
+    if nf == 0 or nv == 0:
+        return seen.view(torch.bool)
+    Hup, Wup = h * upscale, w * upscale
+    zbuf = torch.empty(Hup, Wup, dtype=torch.int64, device=faces.device)
+    L = _lib.lib()
+    for i in range(nv):                                   # launches only: nothing in this loop waits for the device
+        K = np.ascontiguousarray(intrs[i].detach().to("cpu", torch.float32)[:3, :3].contiguous().numpy())
+        w2c = np.ascontiguousarray(torch.inverse(c2ws[i].detach().to("cpu", torch.float32))[:3, :4].contiguous().numpy())
+        zbuf.fill_(-1)
+        _lib.check(L.surf_raster_first_hit(_p(vertices), _p(faces), nf, _np_ptr(K), _np_ptr(w2c), h, w, Hup, Wup, _p(zbuf),
+                                           _stream()), "surf_raster_first_hit")
+        _lib.check(L.surf_clean_mark_visible(_p(zbuf), Hup, Wup, _p(m[i]), h, w, upscale, nf, _p(seen), _stream()),
+                   "surf_clean_mark_visible")
+    return seen.view(torch.bool)
+
+
+def clean_components(faces, min_len, return_labels=False):
+    """clean_mesh.face_components on the device: keep (F,) bool of the faces that share an edge with some face and whose
+    edge-connected component has at least min_len faces.  faces (F, 3) int32.  With return_labels also (root, size): the
+    smallest face id of every face's component and, at the roots, the component's face count."""
+    _chk(faces, torch.int32, "faces")
+    nf, dev = faces.shape[0], faces.device
+    if nf == 0:
+        e = torch.zeros(0, dtype=torch.bool, device=dev)
+        return (e, torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.int32, device=dev)) if return_labels else e
+    L = _lib.lib()
+    slots = L.surf_clean_components_slots(nf)
+    if slots < 0:
+        _lib.check(int(slots), "surf_clean_components_slots")
+    try:
+        keys = torch.empty(slots, dtype=torch.int64, device=dev)
+        owner = torch.empty(slots, dtype=torch.int32, device=dev)
+        shared = torch.empty(slots, dtype=torch.uint8, device=dev)
+        edge_slot = torch.empty(3 * nf, dtype=torch.int32, device=dev)
+        parent = torch.empty(nf, dtype=torch.int32, device=dev)
+        size = torch.empty(nf, dtype=torch.int32, device=dev)
+        has_nb = torch.empty(nf, dtype=torch.uint8, device=dev)
+        keep = torch.empty(nf, dtype=torch.uint8, device=dev)
+    except torch.cuda.OutOfMemoryError:
+        _lib.check(-2, f"surf_clean_components: the edge table of {nf} faces does not fit the device")
+    _lib.check(L.surf_clean_components(_p(faces), nf, int(min(max(int(min_len), -1), 1 << 62)), _p(keys), _p(owner), _p(shared), slots,
+                                       _p(edge_slot), _p(parent), _p(has_nb), _p(size), _p(keep), _stream()), "surf_clean_components")
+    keep = keep.view(torch.bool)
+    return (keep, parent, size) if return_labels else keep
+
+
+def clean_update_faces(vertices, faces, keep, compact_vertices=True):
+    """clean_mesh.update_faces on the device: the kept faces in their order and, with compact_vertices, the vertices they use
+    in their order with the faces renumbered.  vertices (V, 3) of any 4- or 8-byte dtype (returned in that dtype), faces (F, 3)
+    int32, keep (F,) bool / uint8.  One host read (the two counts)."""
+    _chk(faces, torch.int32, "faces")
+    if not torch.is_tensor(vertices) or not vertices.is_contiguous() or vertices.element_size() not in (4, 8):
+        raise TypeError("vertices: expected a contiguous tensor of a 4- or 8-byte dtype")
+    k = keep.view(torch.uint8) if keep.dtype == torch.bool else keep
+    _chk(k, torch.uint8, "keep")
+    nf, nv, dev = faces.shape[0], vertices.shape[0], faces.device
+    if nf == 0 or nv == 0:
+        return (vertices[:0] if compact_vertices else vertices), faces[:0]
+    L = _lib.lib()
+    fscan = torch.cumsum(k, 0, dtype=torch.int64)
+    if compact_vertices:
+        used = torch.zeros(nv, dtype=torch.uint8, device=dev)
+        _lib.check(L.surf_clean_mark_used(_p(faces), _p(k), nf, nv, _p(used), _stream()), "surf_clean_mark_used")
+        vscan = torch.cumsum(used, 0, dtype=torch.int64)
+        n_f, n_v = (int(v) for v in torch.stack([fscan[-1], vscan[-1]]).tolist())
+    else:
+        used = vscan = None
+        n_f, n_v = int(fscan[-1].item()), nv
+    out_f = torch.empty(n_f, 3, dtype=torch.int32, device=dev)
+    if n_f:
+        _lib.check(L.surf_clean_compact_faces(_p(faces), _p(k), _p(fscan), _p(vscan), nf, nv, _p(out_f), _stream()),
+                   "surf_clean_compact_faces")
+    if not compact_vertices:
+        return vertices, out_f
+    out_v = torch.empty(n_v, 3, dtype=vertices.dtype, device=dev)
+    if n_v:
+        _lib.check(L.surf_clean_compact_rows(_p(vertices), vertices.element_size(), _p(used), _p(vscan), nv, _p(out_v), _stream()),
+                   "surf_clean_compact_rows")
+    return out_v, out_f
+
+
 def marching_cubes(u, isovalue=0.0):
     """mcubes.marching_cubes(u, isovalue) (implicit_surface.py:353) on a device lattice u (nx, ny, nz) fp32.
     Returns (vertices (nv, 3) float64, triangles (nt, 3) int32) device tensors, vertices in lattice-index units.
