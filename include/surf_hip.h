@@ -783,6 +783,23 @@ int surf_clean_compact_faces(const int32_t* faces, const uint8_t* keep, const in
 int surf_clean_compact_rows(const void* src, int elem_bytes, const uint8_t* flags, const int64_t* scan, int64_t n, void* out,
                             void* stream);
 
+/*
+ * Per-scene fine-tuning: the ray batch of one view made on the device (surf_amd/datasets/dtu_finetune.py after .to(device);
+ * finetune_rays.hip).  Added under SURF_ABI_VERSION 41 without a bump, like the mesh-cleaning entry points above: nothing
+ * existing changes signature, and a library that lacks them is refused by name.
+ *   surf_finetune_rays: one ray per pixel coordinate of ONE view.  px / py (n_rays) on the device, fp32 (coords_int32 == 0) or
+ *     int32 (!= 0; converted to fp32, exact); kinv (9) = inverse(K)[:3,:3] and c2w (12) = c2w[:3,:4], row-major fp32 on the
+ *     DEVICE; image (h,w,3) and depth (h,w) fp32 on the device.  rays_o / rays_d / color (n_rays,3), pseudo_depth (n_rays) or
+ *     NULL (then depth may be NULL too).  color and pseudo_depth are copies of the texel at (long(py), long(px)) (truncation);
+ *     a pixel outside the image yields zeros.  The fp32 operation order of the directions is fixed and written out in
+ *     finetune_rays.hip's header comment.
+ *   surf_finetune_gather_pts: out[i] = pts[idx[i]], rows of three fp32; idx (n) int32; an index outside [0, n_pts) yields zeros.
+ */
+int surf_finetune_rays(const void* px, const void* py, int coords_int32, int64_t n_rays, const float* kinv, const float* c2w,
+                       const float* image, const float* depth, int h, int w, float* rays_o, float* rays_d, float* color,
+                       float* pseudo_depth, void* stream);
+int surf_finetune_gather_pts(const float* pts, int64_t n_pts, const int32_t* idx, int64_t n, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

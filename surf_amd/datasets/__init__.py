@@ -4,8 +4,9 @@ import torch.distributed as dist
 from torch.utils.data import DataLoader, DistributedSampler, RandomSampler, SequentialSampler
 
 from .dtu import DTUDataset, TanksDataset
+from .dtu_finetune import DTUDatasetFinetune
 
-DATASETS = {"DTUDataset": DTUDataset, "TanksDataset": TanksDataset}
+DATASETS = {"DTUDataset": DTUDataset, "TanksDataset": TanksDataset, "DTUDatasetFinetune": DTUDatasetFinetune}
 
 
 def collect_fn(data):
@@ -13,11 +14,12 @@ def collect_fn(data):
 
 
 def get_loader(conf, mode, distributed, num_workers=8):
-    """datasets/__init__.py:16-43: batch size 1 (one scene + reference view per item), DistributedSampler under DDP."""
+    """datasets/__init__.py:16-43: batch size 1 (one scene + reference view per item), DistributedSampler under DDP;
+    mode "finetune": the dataset itself (runner.py:63), whose get_random_rays / get_rays_at make the batches."""
     name = conf.get_string("dataset_name")
     if name not in DATASETS:
         raise NotImplementedError(f"dataset_name {name!r}: surf_amd ships {sorted(DATASETS)} "
-                                  "(BlendedMVS / ETH3D / the finetune variants of the reference are not built)")
+                                  "(the reference's BlendedMVS / ETH3D readers and its NeuS-format finetune reader are not built)")
     dataset = DATASETS[name](conf, mode)
     if mode == "finetune":
         return dataset

@@ -1580,6 +1580,54 @@ def clean_update_faces(vertices, faces, keep, compact_vertices=True):
     return out_v, out_f
 
 
+# ------------------------------------------------------------------------------------------------
+# per-scene fine-tuning (finetune_rays.hip): the ray batch of one view, made on the device
+# ------------------------------------------------------------------------------------------------
+
+
+def finetune_rays(px, py, kinv, c2w, image, depth=None):
+    """Rays of one view through pixel coordinates (px, py) ((R,) device tensors, both fp32 or both int32).  kinv: (9,) fp32
+    device, inverse(K)[:3, :3] row-major; c2w: (12,) fp32 device, c2w[:3, :4] row-major; image (h, w, 3) fp32, depth (h, w) fp32
+    or None.  Returns rays_o, rays_d, color (R, 3) and pseudo_depth (R,) or None; color / pseudo_depth are the texels at
+    (long(py), long(px)).  The fp32 operation order is the one written out in finetune_rays.hip."""
+    if px.dtype not in (torch.float32, torch.int32) or py.dtype != px.dtype:
+        raise TypeError("px, py: expected two fp32 or two int32 tensors")
+    _chk(px, px.dtype, "px")
+    _chk(py, py.dtype, "py")
+    _chk(kinv, torch.float32, "kinv")
+    _chk(c2w, torch.float32, "c2w")
+    _chk(image, torch.float32, "image")
+    if depth is not None:
+        _chk(depth, torch.float32, "depth")
+    if px.dim() != 1 or py.shape != px.shape or kinv.numel() != 9 or c2w.numel() != 12 or image.dim() != 3 or image.shape[2] != 3 \
+            or (depth is not None and tuple(depth.shape) != tuple(image.shape[:2])):
+        raise ValueError("finetune_rays: px / py (R,), kinv (9,), c2w (12,), image (h, w, 3), depth (h, w)")
+    n, dev = int(px.shape[0]), px.device
+    h, w = int(image.shape[0]), int(image.shape[1])
+    rays_o = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    rays_d = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    color = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    pseudo = torch.empty(n, dtype=torch.float32, device=dev) if depth is not None else None
+    if n:
+        _lib.check(_lib.lib().surf_finetune_rays(_p(px), _p(py), int(px.dtype == torch.int32), n, _p(kinv), _p(c2w), _p(image),
+                                                 _p(depth), h, w, _p(rays_o), _p(rays_d), _p(color), _p(pseudo), _stream()),
+                   "surf_finetune_rays")
+    return rays_o, rays_d, color, pseudo
+
+
+def finetune_gather_pts(pts, idx):
+    """pts[idx] for pts (N, 3) fp32 and idx (M,) int32 on the device."""
+    _chk(pts, torch.float32, "pts")
+    _chk(idx, torch.int32, "idx")
+    if pts.dim() != 2 or pts.shape[1] != 3 or idx.dim() != 1:
+        raise ValueError("finetune_gather_pts: pts (N, 3), idx (M,)")
+    out = torch.empty(idx.shape[0], 3, dtype=torch.float32, device=pts.device)
+    if idx.shape[0]:
+        _lib.check(_lib.lib().surf_finetune_gather_pts(_p(pts), pts.shape[0], _p(idx), idx.shape[0], _p(out), _stream()),
+                   "surf_finetune_gather_pts")
+    return out
+
+
 def marching_cubes(u, isovalue=0.0):
     """mcubes.marching_cubes(u, isovalue) (implicit_surface.py:353) on a device lattice u (nx, ny, nz) fp32.
     Returns (vertices (nv, 3) float64, triangles (nt, 3) int32) device tensors, vertices in lattice-index units.

@@ -33,7 +33,7 @@ def _sync_gradients(model, optimizer):
         dist.all_reduce_gradients([p for g in optimizer.param_groups for p in g["params"]])
 
 
-def _step(model, ipts, targets, loss_fn, optimizer, cos_anneal_ratio, step, mode, sync=True):
+def _step(model, ipts, targets, loss_fn, optimizer, cos_anneal_ratio, step, mode, sync=True, return_outputs=False):
     outputs = model("train", ipts, cos_anneal_ratio=cos_anneal_ratio, step=step)          # runner.py:155
     out = loss_fn(outputs, targets, step=step, mode=mode)                                  # runner.py:159
     optimizer.zero_grad(set_to_none=True)
@@ -41,11 +41,13 @@ def _step(model, ipts, targets, loss_fn, optimizer, cos_anneal_ratio, step, mode
     if sync:
         _sync_gradients(model, optimizer)
     optimizer.step()
-    return {k: (float(v.detach()) if torch.is_tensor(v) else float(v)) for k, v in out.items()}
+    scalars = {k: (float(v.detach()) if torch.is_tensor(v) else float(v)) for k, v in out.items()}
+    return (scalars, outputs) if return_outputs else scalars
 
 
-def finetune_step(model, ipts, targets, loss_fn, optimizer, cos_anneal_ratio=1.0, step=0):
-    """runner.py:300-330 (finetune): any loss mode but "train" - no per-stage depth terms, the volumes are frozen structure."""
+def finetune_step(model, ipts, targets, loss_fn, optimizer, cos_anneal_ratio=1.0, step=0, return_outputs=False):
+    """runner.py:300-330 (finetune): any loss mode but "train" - no per-stage depth terms, the volumes are frozen structure.
+    return_outputs: (scalars, the forward's outputs) instead of the scalars alone (surf_amd.finetune's PSNR, runner.py:325)."""
     core = model.module if _is_ddp(model) else model
     if not core.has_vol:
         raise ValueError("finetune_step drives a has_vol model (SuRF.init_volumes / load_params_vol first)")
@@ -53,7 +55,7 @@ def finetune_step(model, ipts, targets, loss_fn, optimizer, cos_anneal_ratio=1.0
         # the per-scene volumes are (N_s, 7) with N_s depending on the scene: ranks holding different scenes cannot average
         # them (the reference finetunes in a single process, runner.py:62)
         raise RuntimeError("finetune_step: per-scene volumes cannot be averaged over ranks; finetune in a single process")
-    return _step(model, ipts, targets, loss_fn, optimizer, cos_anneal_ratio, step, "finetune")
+    return _step(model, ipts, targets, loss_fn, optimizer, cos_anneal_ratio, step, "finetune", return_outputs=return_outputs)
 
 
 def train_step(model, ipts, targets, loss_fn, optimizer, cos_anneal_ratio=1.0, step=0, sync=True):
