@@ -800,6 +800,21 @@ int surf_finetune_rays(const void* px, const void* py, int coords_int32, int64_t
                        float* pseudo_depth, void* stream);
 int surf_finetune_gather_pts(const float* pts, int64_t n_pts, const int32_t* idx, int64_t n, float* out, void* stream);
 
+/*
+ * Per-vertex mesh attributes (ImplicitSurface.vertex_attributes; vertex_attrs.hip): the stages around the SDF gradient and blend
+ * kernels, which run unchanged over a mesh's vertex list.  Added under SURF_ABI_VERSION 41 without a bump, like the entry
+ * points above.  n >= 2^31 is SURF_E_LIMIT.
+ *   surf_vertex_points: vertices (n,3) on the device, float64 (is_f64 != 0; converted by round-to-nearest-even, as
+ *     torch.Tensor.float()) or fp32 (copied) -> pts (n,3) fp32 and idx (n) int32 = 0 .. n-1, the index list surf_sdf_mlp* and
+ *     surf_blend* take.
+ *   surf_vertex_finish: grad (n,3), color (n,3) fp32 and n_valid (n) uint8 -> normals (n,3) fp32 = grad / |grad| ((0,0,0) where
+ *     |grad| is zero or not finite) and colors (n,3) uint8 = trunc(clamp(color * 256, 0, 255)), (128,128,128) where n_valid is 0.
+ *     The fp32 operation order is fixed and written out in vertex_attrs.hip's header comment.
+ */
+int surf_vertex_points(const void* vertices, int is_f64, int64_t n, float* pts, int32_t* idx, void* stream);
+int surf_vertex_finish(const float* grad, const float* color, const uint8_t* n_valid, int64_t n, float* normals, uint8_t* colors,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@ loader (surf_amd.datasets, the val_dataset block of the HOCON conf)  ->  SuRF(co
 -> model("val", inputs)                                     (runner.py:213-229: FPN, 4-stage volumes, render, SDF lattice, marching cubes)
 -> [clean_mesh with the item's masks, --clean_mesh]         (runner.py:233-234, utils/clean_mesh.py:110-130;
                                                              --clean_backend device: the same cleaned mesh from mesh_clean.hip)
+-> [per-vertex normals + blended colours, --vertex_colors]  (ImplicitSurface.vertex_attributes on the final vertex set)
 -> mesh_io.export_mesh(<out>/meshes/final/scan<N>.ply, scale_mat)   (runner.py:236-240; the file name evaluation/dtu_eval.py reads)
 -> evaluation.dtu_eval.evaluate_scan                        (evaluation/dtu_eval.py:31-190)
 -> one JSON line: {"scan", "d2s", "s2d", "chamfer", "reference_chamfer", "delta", ...}.
@@ -59,6 +60,9 @@ def parse_args(argv=None):
     ap.add_argument("--clean_mesh", action="store_true", help="runner.py --clean_mesh: drop faces outside the dilated masks / frusta")
     ap.add_argument("--clean_backend", default="host", choices=["host", "device"],
                     help="where --clean_mesh runs (device: the HIP kernels of mesh_clean.hip, same cleaned mesh)")
+    ap.add_argument("--vertex_colors", action="store_true",
+                    help="also write per-vertex normals (nx ny nz) and blended colours (red green blue) into the PLY "
+                         "(ImplicitSurface.vertex_attributes on the final vertex set; geometry and Chamfer unchanged)")
     ap.add_argument("--downsample_density", type=float, default=0.2)
     ap.add_argument("--patch_size", type=float, default=60)
     ap.add_argument("--max_dist", type=float, default=20)
@@ -72,7 +76,9 @@ def parse_args(argv=None):
     return ap.parse_args(argv)
 
 
-def run(args):
+def run(args, state=None):
+    """Returns the JSON record.  state (dict, tests): receives the live `model`, the loader's `item` and the final normalised-frame
+    `vertices` / `triangles` of the (last) evaluation."""
     from surf_amd import conf as C
     from surf_amd import mesh_io, synthetic
     from surf_amd.datasets import get_loader
@@ -104,6 +110,8 @@ def run(args):
     item = next(iter(loader))
     inputs = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in item.items()}              # runner.py's tocuda
     inputs["mesh_resolution"] = args.mesh_resolution
+    if args.vertex_colors:
+        inputs["keep_scene"] = True              # the val forward's scene, for the attributes of the (cleaned) vertex set
 
     torch.manual_seed(0)
     model = SuRF(mconf)
@@ -137,7 +145,15 @@ def run(args):
         t_clean = time.perf_counter() - t0
         mesh_path = os.path.join(args.out_dir, "meshes", "final" + tag, f"scan{args.scan}.ply")
         os.makedirs(os.path.dirname(mesh_path), exist_ok=True)
-        mesh_io.export_mesh(mesh_path, v, t, item["scale_mat"])                                   # runner.py:236-240
+        if state is not None:
+            state.update(model=model, item=item, vertices=v, triangles=t)
+        attrs, t_attr = {}, None
+        if args.vertex_colors:                   # on the final vertex set: after clean_mesh, before scale_mat
+            t0 = time.perf_counter()
+            attrs = model.vertex_attributes(v)
+            t_attr = time.perf_counter() - t0
+        mesh_io.export_mesh(mesh_path, v, t, item["scale_mat"], normals=attrs.get("normals"),
+                            colors=attrs.get("colors"))                                           # runner.py:236-240
         t0 = time.perf_counter()
         d2s, s2d, overall = dtu_eval.evaluate_scan(mesh_path, args.eval_dir, args.scan, patch_size=args.patch_size,
                                                    max_dist=args.max_dist, downsample_density=args.downsample_density,
@@ -150,7 +166,8 @@ def run(args):
                 **conv, "sdf_precision": model.implicit_surface.sdf_precision,
                 "checkpoint": args.ckpt, "missing_keys": missing, "unexpected_keys": unexpected, "cleaned": bool(args.clean_mesh),
                 "clean_backend": args.clean_backend if args.clean_mesh else None,
-                "seconds": {"load": t_load, "val_forward": t_val, "clean": t_clean, "evaluate": t_eval}}
+                "seconds": {"load": t_load, "val_forward": t_val, "clean": t_clean, "evaluate": t_eval,
+                            **({} if t_attr is None else {"vertex_attributes": t_attr})}}
 
     if not args.sweep:
         rec = evaluate()

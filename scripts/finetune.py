@@ -3,7 +3,7 @@
 fine-tuning") - as ONE command:
 
     python scripts/finetune.py --conf <surf_finetune.conf> --resume ckpt.pth --scene scan24 --ref_view 23 \
-        [--steps 5000 --mesh_resolution 512 --clean_mesh --out_dir ./outputs] [--eval_dir <DTU eval data> --eval_device gpu]
+        [--steps 5000 --mesh_resolution 512 --clean_mesh --vertex_colors --out_dir ./outputs] [--eval_dir <DTU eval data> --eval_device gpu]
 
 (the conf is the reference's confs/surf_finetune.conf with its paths filled in: this repository ships no confs/ directory)
 
@@ -42,6 +42,8 @@ def parse_args(argv=None):
     ap.add_argument("--mesh_resolution", type=int, default=512)
     ap.add_argument("--clean_mesh", action="store_true", help="clean the validation meshes with the validation item's masks")
     ap.add_argument("--clean_backend", default="host", choices=["host", "device"])
+    ap.add_argument("--vertex_colors", action="store_true",
+                    help="also write per-vertex normals and blended colours into the validation PLYs (geometry unchanged)")
     ap.add_argument("--out_dir", default=None, help="overrides general.base_exp_dir")
     ap.add_argument("--host_batch", action="store_true", help="make the batches on the host and upload them (the reference's path)")
     ap.add_argument("--eval_dir", default=None, help="DTU evaluation data: score the final PLY (scripts/dtu_chamfer.py's evaluator)")
@@ -95,7 +97,8 @@ def run(args, state=None):
     vols0 = [p.detach().clone() for p in model.volumes]
     loss_fn = Loss(cfg["train.loss"]).to(dev)
     res = FT.finetune(model, dataset, loss_fn, cfg, out_dir, steps=args.steps, device=dev, on_device=not args.host_batch,
-                      mesh_resolution=args.mesh_resolution, clean_mesh=args.clean_mesh, clean_backend=args.clean_backend)
+                      mesh_resolution=args.mesh_resolution, clean_mesh=args.clean_mesh, clean_backend=args.clean_backend,
+                      vertex_colors=args.vertex_colors)
     moved = {"implicit_surface": max(float((p.detach() - q).abs().max()) for p, q in zip(model.implicit_surface.parameters(), isurf0)),
              "volumes": max(float((p.detach() - q).abs().max()) for p, q in zip(model.volumes, vols0))}
     rec = {"scene": scene, "ref_view": ref_view, "views": [int(v) for v in dataset.all_views], "steps": res["steps"],

@@ -109,6 +109,8 @@ SIGNATURES = {
     "surf_clean_compact_rows": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
     "surf_finetune_rays": (c_int, [c_ptr, c_ptr, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     "surf_finetune_gather_pts": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr]),
+    "surf_vertex_points": (c_int, [c_ptr, c_int, c_i64, c_ptr, c_ptr, c_ptr]),
+    "surf_vertex_finish": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
     "surf_composite": (c_int, [c_ptr] * 9 + [c_int, c_int, c_float, c_float] + [c_ptr] * 13),
     "surf_upsample_bilinear_t4": (c_int, [c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
     "surf_surface_points": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),

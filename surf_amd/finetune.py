@@ -56,12 +56,17 @@ def save_checkpoint(path, step, model, optimizer, scheduler):
                 "lr_scheduler": scheduler.state_dict()}, path)
 
 
-def validate(model, dataset, out_dir, step, device, mesh_resolution=512, clean_mesh=False, clean_backend="host", val_vid=0):
+def validate(model, dataset, out_dir, step, device, mesh_resolution=512, clean_mesh=False, clean_backend="host", val_vid=0,
+             vertex_colors=False):
     """runner.py:357-396: render the validation lattice of view `val_vid`, extract the mesh, write the world-frame PLY and the
-    image / normal / depth arrays.  Returns {"mesh", "psnr", "color_loss", "triangles", "outputs"}."""
+    image / normal / depth arrays.  Returns {"mesh", "psnr", "color_loss", "triangles", "outputs"}.  vertex_colors (ours): the
+    PLY also carries per-vertex normals and blended colours (SuRF.vertex_attributes on the final - cleaned - vertex set, before
+    scale_mat); positions and faces are the same."""
     item = dataset.get_rays_at(val_vid)
     inputs = to_device(item, device)
     inputs["mesh_resolution"] = mesh_resolution
+    if vertex_colors:
+        inputs["keep_scene"] = True
     was_training = model.training
     with torch.no_grad():
         out = model("val", inputs, cos_anneal_ratio=1.0)
@@ -74,7 +79,8 @@ def validate(model, dataset, out_dir, step, device, mesh_resolution=512, clean_m
         v, t = CM.clean_mesh(v, t, item["masks"], item["intrs"], item["c2ws"], device=str(torch.device(device)), backend=clean_backend)
     mesh_path = os.path.join(out_dir, "meshes", "{}_step{}.ply".format(item["scene"], step))
     os.makedirs(os.path.dirname(mesh_path), exist_ok=True)
-    mesh_io.export_mesh(mesh_path, v, t, item["scale_mat"].cpu())
+    attrs = model.vertex_attributes(v) if vertex_colors and len(v) else {}
+    mesh_io.export_mesh(mesh_path, v, t, item["scale_mat"].cpu(), normals=attrs.get("normals"), colors=attrs.get("colors"))
     for sub, arr in (("val_img", out["img_fine"]), ("val_normal", out["normal_img"])):
         os.makedirs(os.path.join(out_dir, sub), exist_ok=True)
         Image.fromarray(arr.astype(np.uint8)).save(os.path.join(out_dir, sub, "{}_step{}.png".format(val_vid, step)))
@@ -87,11 +93,12 @@ def validate(model, dataset, out_dir, step, device, mesh_resolution=512, clean_m
 
 
 def finetune(model, dataset, loss_fn, conf, out_dir, steps=None, device="cuda:0", on_device=True, mesh_resolution=512,
-             clean_mesh=False, clean_backend="host", validate_mesh=True):
+             clean_mesh=False, clean_backend="host", validate_mesh=True, vertex_colors=False):
     """runner.py:298-398.  model: a has_vol SuRF on `device`; dataset: DTUDatasetFinetune; conf: the whole conf (its `train`
     block: lr_conf, epochs, anneal_end, warmup, alpha, save_freq, val_freq).  steps overrides train.epochs.  Returns
     {"loss", "color_loss", "psnr" (per step), "checkpoints", "meshes", "val" (per validation: psnr, color_loss), "ms_per_step",
-    "ms_per_batch", "steps", "on_device", "optimizer", "lr_scheduler"}.  validate_mesh=False skips the validations (timing runs)."""
+    "ms_per_batch", "steps", "on_device", "optimizer", "lr_scheduler"}.  validate_mesh=False skips the validations (timing runs);
+    vertex_colors: the validation PLYs carry normals and colours (validate)."""
     device = torch.device(device)
     tr = conf["train"]
     total = int(steps) if steps is not None else tr.get_int("epochs")
@@ -133,7 +140,8 @@ def finetune(model, dataset, loss_fn, conf, out_dir, steps=None, device="cuda:0"
             checkpoints.append(os.path.join(out_dir, "checkpoints", "model_{:0>3}.ckpt".format(step)))
             save_checkpoint(checkpoints[-1], step, model, optimizer, scheduler)
         if validate_mesh and ((step + 1) % val_freq == 0 or last):
-            val = validate(model, dataset, out_dir, step, device, mesh_resolution, clean_mesh, clean_backend)
+            val = validate(model, dataset, out_dir, step, device, mesh_resolution, clean_mesh, clean_backend,
+                           vertex_colors=vertex_colors)
             meshes.append(val["mesh"])
             vals.append({"step": step, "psnr": val["psnr"], "color_loss": val["color_loss"], "triangles": val["triangles"]})
     n = max(total, 1)

@@ -215,6 +215,8 @@ class ImplicitSurface(nn.Module):
         self.mesh_band_margin = confs.get_float("render.mesh_band_margin", MESH_BAND_MARGIN)
         if not self.mesh_band_margin >= 0.0:
             raise ValueError(f"render.mesh_band_margin must be >= 0, got {self.mesh_band_margin!r}")
+        # whether a `val` forward also returns per-vertex normals and blended colours of its mesh (vertex_attributes; default off)
+        self.mesh_vertex_attributes = bool(confs.get_bool("render.vertex_attributes", False))
         self._packed = None
         self.kernel_events = None          # bench.py: list receiving (name, start, end) HIP event triples
         self.active_samples_log = None     # bench.py: list receiving the active-sample count of every render call
@@ -649,8 +651,67 @@ class ImplicitSurface(nn.Module):
         vertices, triangles = marching_cubes(u, threshold, rescale=rescale)
         return vertices, triangles
 
+    # device bytes a vertex costs while its chunk is in flight: fp32 point row 12 + index 4 + sdf 4 + gradient 12 + colour 12 + view
+    # count 1 (the kernels' scratch is a bounded per-launch term: vertex_chunk_rows)
+    VERTEX_ROW_BYTES = 45
+    VERTEX_CHUNK = 1 << 22             # rows per launch when memory does not bind: the two MLP kernels are persistent over tiles
+
+    def vertex_chunk_rows(self, device, n_views):
+        """Rows per launch of `vertex_attributes`, sized like val_chunk_rays: VERTEX_CHUNK, at most what half of the free device
+        memory holds after the two kernels' scratch (their scratch-bytes queries), and at most 2^24 rows for the fp32-MFMA SDF
+        kernel (sdf_grid's per-launch bound for it)."""
+        chunk = self.VERTEX_CHUNK if self.sdf_precision != "f32" else min(self.VERTEX_CHUNK, 1 << 24)
+        if torch.device(device).type == "cuda":
+            free, _ = torch.cuda.mem_get_info(device)
+            scratch = ops.vertex_scratch_bytes(chunk, n_views, self.sdf_precision, self.blend_precision)
+            fit = max(0, free // 2 - scratch) // self.VERTEX_ROW_BYTES
+            chunk = int(max(256, min(chunk, (fit // 256) * 256)))
+        return chunk
+
+    @torch.no_grad()
+    def vertex_attributes(self, vertices, scene, chunk=None):
+        """Per-vertex normals and blended colours of an extracted mesh.  vertices: the (V, 3) float64 / float32 array
+        extract_geometry returns (normalised scene frame, before scale_mat), numpy or a device tensor; scene: SceneVolumes.
+        Returns {"normals" (V, 3) float32 = g / |g| with g the SDF gradient at the vertex (sdf_precision's kernel; a zero row where
+        |g| is 0 or not finite), "colors" (V, 3) uint8 = the blending network's colour at the vertex - what render_core computes for
+        a sample there (blend_precision's kernel, every vertex active, no occupancy mask) - quantised like validate's img_fine
+        (clip(c * 256, 0, 255), truncated), grey 128 where no source view sees the vertex, "n_valid" (V,) uint8 = the blend
+        kernel's count of source views the vertex projects into}, arrays of the input's kind (numpy in -> numpy out, one copy to
+        the host).  chunk: rows per launch (default vertex_chunk_rows); the kernels treat rows independently, the result does not
+        depend on it."""
+        as_numpy = not torch.is_tensor(vertices)
+        dev = scene.device
+        v = torch.from_numpy(np.ascontiguousarray(vertices)) if as_numpy else vertices
+        if v.dtype not in (torch.float64, torch.float32) or v.dim() != 2 or v.shape[1] != 3:
+            raise ValueError("vertex_attributes: vertices must be a (V, 3) float64 or float32 array")
+        v = v.detach().to(dev).contiguous()
+        V = int(v.shape[0])
+        chunk = self.vertex_chunk_rows(dev, scene.cams.nv) if chunk is None else int(chunk)
+        if chunk < 1:
+            raise ValueError(f"vertex_attributes: chunk must be >= 1, got {chunk!r}")
+        # one buffer (12 V bytes of normals | 3 V of colours | V of view counts): one copy to the host
+        flat = torch.empty(16 * V, dtype=torch.uint8, device=dev)
+        normals = flat[:12 * V].view(torch.float32).view(V, 3)
+        colors = flat[12 * V:15 * V].view(V, 3)
+        n_valid = flat[15 * V:]
+        if V:
+            sdf_w, blend_w = self.packed_weights(dev)
+        for s in range(0, V, chunk):
+            e = min(V, s + chunk)
+            pts, idx = self._timed_event("vertex_points", lambda: ops.vertex_points(v[s:e]))
+            _, grad = self._timed_event("vertex_sdf", lambda: ops.sdf_mlp(pts, scene.sv, sdf_w, active_idx=idx))
+            col, nv = self._timed_event("vertex_blend", lambda: ops.blend(pts, scene.feats_t4, scene.imgs_t4, scene.cams, blend_w,
+                                                                          active_idx=idx))
+            self._timed_event("vertex_finish", lambda: ops.vertex_finish(grad, col, nv, normals[s:e], colors[s:e]))
+            n_valid[s:e].copy_(nv)
+        if as_numpy:
+            host = flat.cpu().numpy()
+            return {"normals": host[:12 * V].view(np.float32).reshape(V, 3), "colors": host[12 * V:15 * V].reshape(V, 3),
+                    "n_valid": host[15 * V:]}
+        return {"normals": normals, "colors": colors, "n_valid": n_valid}
+
     def validate(self, rays_o, rays_d, near, far, scene, bound_min, bound_max, hw, cos_anneal_ratio=1.0, step=None,
-                 extract_geometry=True, mesh_resolution=512, threshold=0.0, chunk=None):
+                 extract_geometry=True, mesh_resolution=512, threshold=0.0, chunk=None, vertex_attributes=False):
         """implicit_surface.py:359-402.  The reference's 256-ray chunks exist to bound autograd memory; here rays are
         independent, so `chunk` is only a scratch-size knob: default `render.val_chunk` (conf key of ours, 2^19 rays: a 576 x 800
         image in one launch of every kernel - eight 65,536-ray chunks cost 6 ms more per image in launch tails and small
@@ -659,7 +720,9 @@ class ImplicitSurface(nn.Module):
         (`--one-gpu`, scene-parallel runs on fewer GPUs than ranks) then shrink their chunks instead of running out of memory.
         With render.perturb > 0 the jitters are drawn in the
         reference's order (per 256-ray block, stages inner: draw_jitter), so a seeded run reproduces the reference's
-        sample positions whatever `chunk` is."""
+        sample positions whatever `chunk` is.
+        vertex_attributes (ours; forward() passes render.vertex_attributes): when a mesh was extracted, also `vertex_normals`,
+        `vertex_colors` and `vertex_n_valid` (self.vertex_attributes on the mesh's vertices); off, the outputs are untouched."""
         outputs = {}
         height, width = int(hw[0]), int(hw[1])
         cols, nrms, sdeps, rdeps = [], [], [], []
@@ -687,6 +750,10 @@ class ImplicitSurface(nn.Module):
             v, t = self.extract_geometry(None, None, bound_min, bound_max, mesh_resolution, threshold, scene=scene,
                                          mesh_extraction=self.mesh_extraction)
             outputs["vertices"], outputs["triangles"] = v, t
+            if vertex_attributes:                # render.vertex_attributes (conf key of ours): normals + blended colours of the mesh
+                attrs = self.vertex_attributes(v, scene)
+                outputs["vertex_normals"], outputs["vertex_colors"] = attrs["normals"], attrs["colors"]
+                outputs["vertex_n_valid"] = attrs["n_valid"]
         if copied is not None:
             copied.synchronize()
         outputs["color_fine"] = host[:3 * R].view(R, 3)
@@ -755,7 +822,7 @@ class ImplicitSurface(nn.Module):
                 scene.match_feats_t4 = [ops.pack_texel4(f.detach().float().contiguous()) for f in match_features]
             if mode == "val":
                 outputs = self.validate(rays_o, rays_d, near, far, scene, ipts["bound_min"], ipts["bound_max"], ipts["hw"],
-                                        cos_anneal_ratio, step)
+                                        cos_anneal_ratio, step, vertex_attributes=self.mesh_vertex_attributes)
                 if "pseudo_pts" in ipts:  # implicit_surface.py:425-434
                     outputs["pseudo_sdf"] = self.pseudo_sdf(ipts["pseudo_pts"], scene)
                 return outputs

@@ -1,7 +1,8 @@
 """Mesh export of the validation loop (runner.py:231-240): the reference builds a `trimesh.Trimesh(vertices, triangles)`,
 applies the scene's `scale_mat` (normalised unit-sphere frame -> world frame, datasets/dtu.py:204-240) and exports a PLY.
 trimesh is not a dependency here: `transform_vertices` is `Trimesh.apply_transform` for a point set and `write_ply` writes
-the same binary little-endian PLY layout trimesh 3.22 exports (float32 x y z, faces as `list uchar int vertex_indices`)."""
+the same binary little-endian PLY layout trimesh 3.22 exports (float32 x y z, faces as `list uchar int vertex_indices`).
+Optional per-vertex attributes (ImplicitSurface.vertex_attributes): float32 normals `nx ny nz`, uint8 colours `red green blue`."""
 import os
 
 import numpy as np
@@ -18,15 +19,54 @@ def transform_vertices(vertices, matrix):
     return out
 
 
-def write_ply(path, vertices, triangles):
-    """Binary little-endian PLY: `element vertex N` (float x, y, z) + `element face M` (list uchar int vertex_indices)."""
+def transform_normals(normals, matrix, rtol=1e-4):
+    """(V,3) unit normals through the linear part of a 4x4 similarity transform (rotation times uniform scale, what scale_mat is
+    for the DTU and the Tanks readers), re-normalised; zero rows stay zero.  A similarity has A A^T = s^2 I: checked to `rtol`
+    relative to s^2, ValueError otherwise (normals would need the inverse transpose, and the mesh would be sheared)."""
+    m = np.asarray(matrix, dtype=np.float64).reshape(4, 4)
+    a = m[:3, :3]
+    gram = a @ a.T
+    s2 = np.trace(gram) / 3.0
+    if not (np.isfinite(gram).all() and s2 > 0 and np.abs(gram - s2 * np.eye(3)).max() <= rtol * s2
+            and np.abs(m[3, :3]).max() <= rtol * abs(m[3, 3])):
+        raise ValueError("transform_normals: the matrix is not a rotation times a uniform scale")
+    n = np.asarray(normals, dtype=np.float64).reshape(-1, 3) @ a.T
+    length = np.linalg.norm(n, axis=1, keepdims=True)
+    return np.where(length > 0, n / np.where(length > 0, length, 1.0), 0.0).astype(np.float32)
+
+
+def write_ply(path, vertices, triangles, normals=None, colors=None):
+    """Binary little-endian PLY: `element vertex N` (float x, y, z [, float nx, ny, nz] [, uchar red, green, blue]) +
+    `element face M` (list uchar int vertex_indices).  normals: (N,3) float32, colors: (N,3) uint8, both optional; without them
+    the file is the bare-geometry file, byte for byte."""
     v = np.ascontiguousarray(np.asarray(vertices, dtype="<f4").reshape(-1, 3))
     t = np.ascontiguousarray(np.asarray(triangles, dtype="<i4").reshape(-1, 3))
     if t.size and (t.min() < 0 or t.max() >= max(len(v), 1)):
         raise ValueError("triangle index out of range")
+    fields, props = [("xyz", "<f4", (3,))], "property float x\nproperty float y\nproperty float z\n"
+    if normals is not None:
+        normals = np.asarray(normals, dtype="<f4")
+        if normals.shape != v.shape:
+            raise ValueError("normals: expected one (x, y, z) row per vertex")
+        fields.append(("n", "<f4", (3,)))
+        props += "property float nx\nproperty float ny\nproperty float nz\n"
+    if colors is not None:
+        colors = np.asarray(colors)
+        if colors.dtype != np.uint8 or colors.shape != v.shape:
+            raise ValueError("colors: expected one uint8 (red, green, blue) row per vertex")
+        fields.append(("rgb", "u1", (3,)))
+        props += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
     header = ("ply\nformat binary_little_endian 1.0\ncomment surf_amd mesh export\n"
-              f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
+              f"element vertex {len(v)}\n{props}"
               f"element face {len(t)}\nproperty list uchar int vertex_indices\nend_header\n")
+    if len(fields) > 1:
+        rows = np.empty(len(v), dtype=fields)               # packed: 12 [+ 12] [+ 3] bytes per vertex
+        rows["xyz"] = v
+        if normals is not None:
+            rows["n"] = normals
+        if colors is not None:
+            rows["rgb"] = colors
+        v = rows
     faces = np.empty(len(t), dtype=[("n", "u1"), ("idx", "<i4", (3,))])
     faces["n"] = 3
     faces["idx"] = t
@@ -37,8 +77,15 @@ def write_ply(path, vertices, triangles):
         f.write(faces.tobytes())
 
 
-def read_ply(path):
-    """Reads back what write_ply (or trimesh's binary PLY export of a plain triangle mesh) wrote."""
+_PLY_TYPES = {"float": "<f4", "float32": "<f4", "double": "<f8", "float64": "<f8", "uchar": "u1", "uint8": "u1", "char": "i1",
+              "int8": "i1", "short": "<i2", "int16": "<i2", "ushort": "<u2", "uint16": "<u2", "int": "<i4", "int32": "<i4",
+              "uint": "<u4", "uint32": "<u4"}
+
+
+def read_ply(path, attributes=False):
+    """Reads back what write_ply (or trimesh's binary PLY export of a plain triangle mesh) wrote: (vertices, triangles).
+    attributes=True: (vertices, triangles, {"normals": (N,3) float32, "colors": (N,3) uint8}) with the properties the file has
+    (nx ny nz / red green blue); vertex properties beyond those are skipped."""
     with open(path, "rb") as f:
         data = f.read()
     end = data.index(b"end_header\n") + len(b"end_header\n")
@@ -46,22 +93,47 @@ def read_ply(path):
     if "format binary_little_endian 1.0" not in head:
         raise ValueError("only binary little-endian PLY is supported")
     nv = nt = 0
+    element, vprops = None, []
     for l in head:
+        w = l.split()
+        if l.startswith("element"):
+            element = w[1]
         if l.startswith("element vertex"):
-            nv = int(l.split()[-1])
+            nv = int(w[-1])
         if l.startswith("element face"):
-            nt = int(l.split()[-1])
-    v = np.frombuffer(data, dtype="<f4", count=nv * 3, offset=end).reshape(nv, 3)
-    faces = np.frombuffer(data, dtype=[("n", "u1"), ("idx", "<i4", (3,))], count=nt, offset=end + nv * 12)
+            nt = int(w[-1])
+        if l.startswith("property") and element == "vertex":
+            if w[1] == "list" or w[1] not in _PLY_TYPES:
+                raise ValueError(f"unsupported vertex property: {l}")
+            vprops.append((w[2], _PLY_TYPES[w[1]]))
+    vdt = np.dtype(vprops)
+    if [n for n, _ in vprops[:3]] != ["x", "y", "z"] or any(vdt[n] != np.dtype("<f4") for n in ("x", "y", "z")):
+        raise ValueError("expected float x, y, z as the first vertex properties")
+    rows = np.frombuffer(data, dtype=vdt, count=nv, offset=end)
+    v = np.stack([rows["x"], rows["y"], rows["z"]], axis=1).reshape(nv, 3)
+    faces = np.frombuffer(data, dtype=[("n", "u1"), ("idx", "<i4", (3,))], count=nt, offset=end + nv * vdt.itemsize)
     if nt and not (faces["n"] == 3).all():
         raise ValueError("not a triangle mesh")
-    return v.copy(), faces["idx"].copy()
+    if not attributes:
+        return v.copy(), faces["idx"].copy()
+    attrs = {}
+    names = set(vdt.names)
+    if {"nx", "ny", "nz"} <= names:
+        attrs["normals"] = np.stack([rows["nx"], rows["ny"], rows["nz"]], axis=1).reshape(nv, 3).astype(np.float32)
+    if {"red", "green", "blue"} <= names:
+        attrs["colors"] = np.stack([rows["red"], rows["green"], rows["blue"]], axis=1).reshape(nv, 3).astype(np.uint8)
+    return v.copy(), faces["idx"].copy(), attrs
 
 
-def export_mesh(path, vertices, triangles, scale_mat=None):
-    """runner.py:231-240: optional scale_mat transform, then PLY export.  Returns the transformed vertices."""
+def export_mesh(path, vertices, triangles, scale_mat=None, normals=None, colors=None):
+    """runner.py:231-240: optional scale_mat transform, then PLY export.  Returns the transformed vertices.  normals / colors
+    (per vertex, optional): written as nx ny nz / red green blue; normals go through scale_mat's linear part (transform_normals:
+    scale_mat must then be a rotation times a uniform scale, ValueError otherwise)."""
     v = np.asarray(vertices, dtype=np.float64)
     if scale_mat is not None:
-        v = transform_vertices(v, scale_mat.detach().cpu().numpy() if hasattr(scale_mat, "detach") else scale_mat)
-    write_ply(path, v, triangles)
+        scale_mat = scale_mat.detach().cpu().numpy() if hasattr(scale_mat, "detach") else scale_mat
+        v = transform_vertices(v, scale_mat)
+        if normals is not None:
+            normals = transform_normals(normals, scale_mat)
+    write_ply(path, v, triangles, normals=normals, colors=colors)
     return v

@@ -1628,6 +1628,58 @@ def finetune_gather_pts(pts, idx):
     return out
 
 
+# ------------------------------------------------------------------------------------------------
+# per-vertex mesh attributes (vertex_attrs.hip): the stages around sdf_mlp / blend over a vertex list
+# ------------------------------------------------------------------------------------------------
+
+
+def vertex_points(vertices):
+    """Mesh vertices (V, 3), float64 or fp32 on the device -> (pts (V, 3) fp32, idx (V,) int32 = 0 .. V-1): the point rows and the
+    identity index list sdf_mlp / blend take as active_idx.  float64 -> fp32 rounds to nearest, as torch.Tensor.float()."""
+    if not torch.is_tensor(vertices) or vertices.dtype not in (torch.float64, torch.float32):
+        raise TypeError("vertices: expected a float64 or float32 tensor")
+    _chk(vertices, vertices.dtype, "vertices")
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError("vertex_points: vertices (V, 3)")
+    n, dev = int(vertices.shape[0]), vertices.device
+    pts = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    idx = torch.empty(n, dtype=torch.int32, device=dev)
+    if n:
+        _lib.check(_lib.lib().surf_vertex_points(_p(vertices), int(vertices.dtype == torch.float64), n, _p(pts), _p(idx), _stream()),
+                   "surf_vertex_points")
+    return pts, idx
+
+
+def vertex_finish(grad, color, n_valid, normals=None, colors=None):
+    """SDF gradients (V, 3) fp32, blend colours (V, 3) fp32 and view counts (V,) uint8 -> (normals (V, 3) fp32 = grad / |grad|,
+    zero rows where |grad| is 0 or not finite; colors (V, 3) uint8 = trunc(clamp(color * 256, 0, 255)), grey 128 where n_valid is
+    0).  normals / colors: optional outputs to write into.  The fp32 operation order is the one written out in vertex_attrs.hip."""
+    _chk(grad, torch.float32, "grad")
+    _chk(color, torch.float32, "color")
+    _chk(n_valid, torch.uint8, "n_valid")
+    n, dev = int(n_valid.shape[0]), grad.device
+    if tuple(grad.shape) != (n, 3) or tuple(color.shape) != (n, 3) or n_valid.dim() != 1:
+        raise ValueError("vertex_finish: grad (V, 3), color (V, 3), n_valid (V,)")
+    normals = torch.empty(n, 3, dtype=torch.float32, device=dev) if normals is None else _chk(normals, torch.float32, "normals")
+    colors = torch.empty(n, 3, dtype=torch.uint8, device=dev) if colors is None else _chk(colors, torch.uint8, "colors")
+    if tuple(normals.shape) != (n, 3) or tuple(colors.shape) != (n, 3):
+        raise ValueError("vertex_finish: normals (V, 3), colors (V, 3)")
+    if n:
+        _lib.check(_lib.lib().surf_vertex_finish(_p(grad), _p(color), _p(n_valid), n, _p(normals), _p(colors), _stream()),
+                   "surf_vertex_finish")
+    return normals, colors
+
+
+def vertex_scratch_bytes(n, nv, sdf_precision, blend_precision):
+    """Device scratch the SDF gradient kernel and the blend kernel take for a launch over n points (their scratch-bytes queries)."""
+    L = _lib.lib()
+    fn = "surf_sdf_scratch_bytes" if sdf_precision == "f32" else f"surf_sdf_{_SPLIT_ABI[sdf_precision]}_scratch_bytes"
+    need = int(getattr(L, fn)(int(n)))
+    if blend_precision != "f32":
+        need += int(L.surf_blend_split_scratch_bytes(int(n), int(nv)))
+    return need
+
+
 def marching_cubes(u, isovalue=0.0):
     """mcubes.marching_cubes(u, isovalue) (implicit_surface.py:353) on a device lattice u (nx, ny, nz) fp32.
     Returns (vertices (nv, 3) float64, triangles (nt, 3) int32) device tensors, vertices in lattice-index units.

@@ -383,7 +383,8 @@ class SuRF(nn.Module):
             far = far.repeat(rays_o.shape[0], 1)
         if mode == "val":
             return isurf.validate(rays_o, rays_d, near, far, scene, ipts["bound_min"], ipts["bound_max"], ipts["hw"],
-                                  cos_anneal_ratio, step, mesh_resolution=int(ipts.get("mesh_resolution", 512)))
+                                  cos_anneal_ratio, step, mesh_resolution=int(ipts.get("mesh_resolution", 512)),
+                                  vertex_attributes=isurf.mesh_vertex_attributes)
         surface = isurf.render_scene(rays_o, rays_d, near, far, scene, cos_anneal_ratio, patch_warp=True, step=step)
         if "pseudo_pts" in ipts:                                            # implicit_surface.py:425-434
             surface["pseudo_sdf"] = isurf.pseudo_sdf(ipts["pseudo_pts"], scene)
@@ -418,5 +419,15 @@ class SuRF(nn.Module):
                 outputs, volumes, tables, mvol, features, cams, tape = self.run_build(mode, ipts, record=record)
                 self._train_tape = tape
                 scene = self.build_scene(mode, ipts, volumes, tables, mvol, features, cams, step, match=match)
+            # ipts["keep_scene"] (ours): a caller that colours the mesh AFTER cleaning it (vertex_attributes below) asks for the
+            # scene of this val forward to be kept; otherwise nothing outlives the call
+            self.val_scene = scene if mode == "val" and ipts.get("keep_scene") else None
             outputs.update(self.run_render(mode, ipts, scene, cos_anneal_ratio, step))
             return outputs
+
+    def vertex_attributes(self, vertices, chunk=None):
+        """ImplicitSurface.vertex_attributes on the scene of the last `val` forward that was called with ipts["keep_scene"]: the
+        normals and blended colours of (a cleaned subset of) that forward's mesh vertices, normalised frame."""
+        if getattr(self, "val_scene", None) is None:
+            raise RuntimeError("vertex_attributes: no kept scene (run a val forward with ipts['keep_scene'] = True first)")
+        return self.implicit_surface.vertex_attributes(vertices, self.val_scene, chunk=chunk)
