@@ -784,6 +784,28 @@ int surf_clean_compact_rows(const void* src, int elem_bytes, const uint8_t* flag
                             void* stream);
 
 /*
+ * The DTU evaluation protocol's mesh cleaner on the device (surf_amd/evaluation/clean_dtu.py, backend="device"; dtu_clean.hip).
+ * Every stage returns what the host stage returns.  Added under SURF_ABI_VERSION 41 without a bump, like the entry points above.
+ * Compaction by vertex flag goes through surf_clean_compact_rows / surf_clean_compact_faces; the frustum stage through
+ * surf_raster_first_hit, surf_clean_mark_visible and surf_clean_components.
+ *   surf_dtu_clean_dilate: out = maximum of masks (n_views,h,w) uint8 over a footprint of k rows (k odd, <= 64: SURF_E_LIMIT
+ *     beyond) given as half_widths (k) int32 on the DEVICE: row i covers columns [-half_widths[i], half_widths[i]] of image row
+ *     y + i - k/2 (negative: empty row).  Pixels outside the image do not contribute.
+ *   surf_dtu_clean_points_in_masks: count[v] = number of views whose padded mask is set at the rounded projection of vertex v.
+ *     vertices (n,3) float64; dilated (n_views,h,w) uint8, set where > 128; proj (n_views,12) fp32 on the DEVICE: the first
+ *     three rows of K4 @ E, row-major.  The one-pixel ring of ones around the mask is arithmetic.  The float64 operation order
+ *     is fixed and written out in dtu_clean.hip's header comment.
+ *   surf_dtu_clean_keep: vertex_keep[v] = count[v] > minimal_vis; face_keep[f] = the three vertices of f are kept (an index
+ *     outside [0, n_vertices) drops the face).  n_faces may be 0 (faces / face_keep then unused).
+ */
+int surf_dtu_clean_dilate(const uint8_t* masks, int n_views, int h, int w, const int32_t* half_widths, int k, uint8_t* out,
+                          void* stream);
+int surf_dtu_clean_points_in_masks(const double* vertices, int64_t n_vertices, const uint8_t* dilated, const float* proj,
+                                   int n_views, int h, int w, int32_t* count, void* stream);
+int surf_dtu_clean_keep(const int32_t* count, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int minimal_vis,
+                        uint8_t* vertex_keep, uint8_t* face_keep, void* stream);
+
+/*
  * Per-scene fine-tuning: the ray batch of one view made on the device (surf_amd/datasets/dtu_finetune.py after .to(device);
  * finetune_rays.hip).  Added under SURF_ABI_VERSION 41 without a bump, like the mesh-cleaning entry points above: nothing
  * existing changes signature, and a library that lacks them is refused by name.

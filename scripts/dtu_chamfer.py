@@ -7,6 +7,8 @@ loader (surf_amd.datasets, the val_dataset block of the HOCON conf)  ->  SuRF(co
 -> model("val", inputs)                                     (runner.py:213-229: FPN, 4-stage volumes, render, SDF lattice, marching cubes)
 -> [clean_mesh with the item's masks, --clean_mesh]         (runner.py:233-234, utils/clean_mesh.py:110-130;
                                                              --clean_backend device: the same cleaned mesh from mesh_clean.hip)
+   or, with --clean_protocol dtu_test, AFTER scale_mat:      (evaluation/clean_mesh.py, the cleaner of the published numbers:
+   clean_dtu.clean_dtu_scan with --dtu_test_dir's masks       world millimetres, DTU_TEST object masks, view set --clean_set)
 -> [per-vertex normals + blended colours, --vertex_colors]  (ImplicitSurface.vertex_attributes on the final vertex set)
 -> mesh_io.export_mesh(<out>/meshes/final/scan<N>.ply, scale_mat)   (runner.py:236-240; the file name evaluation/dtu_eval.py reads)
 -> evaluation.dtu_eval.evaluate_scan                        (evaluation/dtu_eval.py:31-190)
@@ -60,6 +62,11 @@ def parse_args(argv=None):
     ap.add_argument("--clean_mesh", action="store_true", help="runner.py --clean_mesh: drop faces outside the dilated masks / frusta")
     ap.add_argument("--clean_backend", default="host", choices=["host", "device"],
                     help="where --clean_mesh runs (device: the HIP kernels of mesh_clean.hip, same cleaned mesh)")
+    ap.add_argument("--clean_protocol", default="runner", choices=["runner", "dtu_test"],
+                    help="which cleaner --clean_mesh runs: runner.py's (the loader's masks, normalised frame) or the DTU evaluation "
+                         "protocol's (evaluation/clean_mesh.py: --dtu_test_dir's object masks, world frame, after scale_mat)")
+    ap.add_argument("--dtu_test_dir", default=None, help="DTU_TEST tree (cameras/, scan<N>/mask/) of --clean_protocol dtu_test")
+    ap.add_argument("--clean_set", type=int, default=1, choices=[0, 1], help="view set of --clean_protocol dtu_test")
     ap.add_argument("--vertex_colors", action="store_true",
                     help="also write per-vertex normals (nx ny nz) and blended colours (red green blue) into the PLY "
                          "(ImplicitSurface.vertex_attributes on the final vertex set; geometry and Chamfer unchanged)")
@@ -82,11 +89,15 @@ def run(args, state=None):
     from surf_amd import conf as C
     from surf_amd import mesh_io, synthetic
     from surf_amd.datasets import get_loader
+    from surf_amd.evaluation import clean_dtu
     from surf_amd.evaluation import clean_mesh as CM
     from surf_amd.evaluation import dtu_eval
     from surf_amd.surf import SuRF
 
     dev = torch.device(args.device)
+    protocol = args.clean_protocol if args.clean_mesh else None
+    if protocol == "dtu_test" and args.dtu_test_dir is None:
+        raise SystemExit("dtu_chamfer: --clean_protocol dtu_test needs --dtu_test_dir")
     cfg = C.parse_file(args.conf)
     dconf = cfg["val_dataset"]
     if args.data_dir is not None:
@@ -140,7 +151,7 @@ def run(args, state=None):
                 return {"scan": args.scan, "chamfer": None, "error": "empty mesh", **conv}
             raise SystemExit("dtu_chamfer: the SDF lattice has no zero crossing inside the bounding box (empty mesh)")
         t0 = time.perf_counter()
-        if args.clean_mesh:
+        if protocol == "runner":
             v, t = CM.clean_mesh(v, t, item["masks"], item["intrs"], item["c2ws"], device=dev.type, backend=args.clean_backend)
         t_clean = time.perf_counter() - t0
         mesh_path = os.path.join(args.out_dir, "meshes", "final" + tag, f"scan{args.scan}.ply")
@@ -152,8 +163,24 @@ def run(args, state=None):
             t0 = time.perf_counter()
             attrs = model.vertex_attributes(v)
             t_attr = time.perf_counter() - t0
-        mesh_io.export_mesh(mesh_path, v, t, item["scale_mat"], normals=attrs.get("normals"),
-                            colors=attrs.get("colors"))                                           # runner.py:236-240
+        if protocol == "dtu_test":               # the protocol's order: world-frame mesh first, then its cleaner, then the file
+            scale_mat = item["scale_mat"].detach().cpu().numpy()
+            vw = mesh_io.transform_vertices(v, scale_mat)
+            t0 = time.perf_counter()
+            vw, t, kept = clean_dtu.clean_dtu_scan(vw, t, args.dtu_test_dir, args.scan, view_set=args.clean_set,
+                                                   backend=args.clean_backend, device=dev.type, return_index=True)
+            t_clean = time.perf_counter() - t0
+            v = np.asarray(v)[kept]
+            if state is not None:
+                state.update(vertices=v, triangles=t)
+            normals = attrs.get("normals")
+            if normals is not None:
+                normals = mesh_io.transform_normals(normals[kept], scale_mat)
+            colors = attrs.get("colors")
+            mesh_io.write_ply(mesh_path, vw, t, normals=normals, colors=None if colors is None else colors[kept])
+        else:
+            mesh_io.export_mesh(mesh_path, v, t, item["scale_mat"], normals=attrs.get("normals"),
+                                colors=attrs.get("colors"))                                       # runner.py:236-240
         t0 = time.perf_counter()
         d2s, s2d, overall = dtu_eval.evaluate_scan(mesh_path, args.eval_dir, args.scan, patch_size=args.patch_size,
                                                    max_dist=args.max_dist, downsample_density=args.downsample_density,
@@ -165,7 +192,7 @@ def run(args, state=None):
                 "views": int(item["imgs"].shape[0]), "render_hw": [int(x) for x in out["img_fine"].shape[:2]],
                 **conv, "sdf_precision": model.implicit_surface.sdf_precision,
                 "checkpoint": args.ckpt, "missing_keys": missing, "unexpected_keys": unexpected, "cleaned": bool(args.clean_mesh),
-                "clean_backend": args.clean_backend if args.clean_mesh else None,
+                "clean_backend": args.clean_backend if args.clean_mesh else None, "clean_protocol": protocol,
                 "seconds": {"load": t_load, "val_forward": t_val, "clean": t_clean, "evaluate": t_eval,
                             **({} if t_attr is None else {"vertex_attributes": t_attr})}}
 

@@ -107,6 +107,9 @@ SIGNATURES = {
     "surf_clean_mark_used": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
     "surf_clean_compact_faces": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
     "surf_clean_compact_rows": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
+    "surf_dtu_clean_dilate": (c_int, [c_ptr, c_int, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr]),
+    "surf_dtu_clean_points_in_masks": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr]),
+    "surf_dtu_clean_keep": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr]),
     "surf_finetune_rays": (c_int, [c_ptr, c_ptr, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     "surf_finetune_gather_pts": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr]),
     "surf_vertex_points": (c_int, [c_ptr, c_int, c_i64, c_ptr, c_ptr, c_ptr]),

@@ -125,6 +125,62 @@ def read_ply(path, attributes=False):
     return v.copy(), faces["idx"].copy(), attrs
 
 
+def read_ply_mesh(path):
+    """(vertices (V,3) float64, faces (F,3) int64) of an ascii or binary little-endian PLY triangle mesh, as this project writes
+    them (write_ply; mvs_io.read_ply_points reads the points only): scalar vertex properties of which x, y, z are taken, then one
+    face element with a single list property of three indices per face.  What trimesh.load returns for such a file, minus its
+    merging of duplicate vertices."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.index(b"end_header") + len(b"end_header")
+    end = data.index(b"\n", end) + 1
+    fmt, element, nv, nt, vprops, fprop = None, None, 0, 0, [], None
+    for l in data[:end].decode("ascii", "ignore").splitlines():
+        w = l.split()
+        if not w:
+            continue
+        if w[0] == "format":
+            fmt = w[1]
+        elif w[0] == "element":
+            element = w[1]
+            if element == "vertex":
+                nv = int(w[2])
+            elif element == "face":
+                nt = int(w[2])
+            elif int(w[2]):
+                raise ValueError(f"unsupported PLY element: {l}")
+        elif w[0] == "property" and element == "vertex":
+            if w[1] == "list" or w[1] not in _PLY_TYPES:
+                raise ValueError(f"unsupported vertex property: {l}")
+            vprops.append((w[2], _PLY_TYPES[w[1]]))
+        elif w[0] == "property" and element == "face":
+            if fprop is not None or w[1] != "list" or w[2] not in _PLY_TYPES or w[3] not in _PLY_TYPES:
+                raise ValueError(f"unsupported face property: {l}")
+            fprop = (_PLY_TYPES[w[2]], _PLY_TYPES[w[3]])
+    names = [n for n, _ in vprops]
+    if not all(a in names for a in "xyz") or (nt and fprop is None):
+        raise ValueError("expected x, y, z vertex properties and a face list property")
+    if fmt == "ascii":
+        lines = data[end:].decode("ascii").split("\n")
+        rows = np.array([l.split() for l in lines[:nv]], dtype=np.float64).reshape(nv, len(names))
+        v = np.stack([rows[:, names.index(a)] for a in "xyz"], axis=1).reshape(nv, 3)
+        faces = np.array([l.split() for l in lines[nv:nv + nt]], dtype=np.int64).reshape(nt, -1)
+        if nt and (faces.shape[1] != 4 or not (faces[:, 0] == 3).all()):
+            raise ValueError("not a triangle mesh")
+        return v, faces[:, 1:].copy() if nt else np.zeros((0, 3), dtype=np.int64)
+    if fmt != "binary_little_endian":
+        raise ValueError("only ascii and binary little-endian PLY are supported")
+    vdt = np.dtype(vprops)
+    rows = np.frombuffer(data, dtype=vdt, count=nv, offset=end)
+    v = np.stack([rows[a].astype(np.float64) for a in "xyz"], axis=1).reshape(nv, 3)
+    if not nt:
+        return v, np.zeros((0, 3), dtype=np.int64)
+    faces = np.frombuffer(data, dtype=[("n", fprop[0]), ("idx", fprop[1], (3,))], count=nt, offset=end + nv * vdt.itemsize)
+    if not (faces["n"] == 3).all():
+        raise ValueError("not a triangle mesh")
+    return v, faces["idx"].astype(np.int64)
+
+
 def export_mesh(path, vertices, triangles, scale_mat=None, normals=None, colors=None):
     """runner.py:231-240: optional scale_mat transform, then PLY export.  Returns the transformed vertices.  normals / colors
     (per vertex, optional): written as nx ny nz / red green blue; normals go through scale_mat's linear part (transform_normals:

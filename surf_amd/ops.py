@@ -1581,6 +1581,80 @@ def clean_update_faces(vertices, faces, keep, compact_vertices=True):
 
 
 # ------------------------------------------------------------------------------------------------
+# the DTU protocol's mesh cleaner (dtu_clean.hip): elliptical dilation, rounded projection into padded masks, vertex removal
+# ------------------------------------------------------------------------------------------------
+
+
+def dtu_clean_dilate(masks, half_widths):
+    """Maximum of every (h, w) slice of masks (nv, h, w) uint8 over the footprint whose row i covers the columns
+    [-half_widths[i], half_widths[i]] (clean_dtu.dilate_ellipse with clean_dtu.ellipse_half_widths); returns uint8."""
+    _chk(masks, torch.uint8, "masks")
+    assert masks.dim() == 3
+    half = [int(x) for x in half_widths]
+    if len(half) % 2 == 0 or len(half) > 64:
+        raise ValueError("the footprint needs an odd number of rows, at most 63")
+    out = torch.empty_like(masks)
+    if masks.numel():
+        nv, h, w = masks.shape
+        hw = torch.tensor(half, dtype=torch.int32).to(masks.device)
+        _lib.check(_lib.lib().surf_dtu_clean_dilate(_p(masks), nv, h, w, _p(hw), len(half), _p(out), _stream()),
+                   "surf_dtu_clean_dilate")
+    return out
+
+
+def dtu_clean_points_in_masks(vertices, dilated, proj):
+    """clean_dtu.points_in_masks on the device: per-vertex number of views whose padded mask holds the vertex, int32.
+    vertices (n, 3) float64, dilated (nv, h, w) uint8 (set where > 128) on the device; proj (nv, 4, 4) or (nv, 3, 4) float32,
+    host or device."""
+    _chk(vertices, torch.float64, "vertices")
+    _chk(dilated, torch.uint8, "dilated")
+    nv, h, w = dilated.shape
+    n = vertices.shape[0]
+    count = torch.zeros(n, dtype=torch.int32, device=vertices.device)
+    if n == 0 or nv == 0:
+        return count
+    P = torch.as_tensor(proj)
+    if P.dtype != torch.float32 or P.shape[0] != nv or tuple(P.shape[1:]) not in ((4, 4), (3, 4)):
+        raise TypeError("proj: expected (n_views, 4, 4) or (n_views, 3, 4) float32")
+    P = P[:, :3, :].contiguous().to(vertices.device)
+    _lib.check(_lib.lib().surf_dtu_clean_points_in_masks(_p(vertices), n, _p(dilated), _p(P), nv, h, w, _p(count), _stream()),
+               "surf_dtu_clean_points_in_masks")
+    return count
+
+
+def dtu_clean_remove_vertices(vertices, faces, count, minimal_vis):
+    """clean_dtu.clean_faces_by_mask on the device: the vertices with count > minimal_vis in their order (referenced or not) and
+    the faces whose three vertices are kept, renumbered.  vertices (V, 3) of a 4- or 8-byte dtype, faces (F, 3) int32, count
+    (V,) int32.  Returns (vertices, faces, the (V,) bool vertex flags).  One host read (the two counts)."""
+    _chk(faces, torch.int32, "faces")
+    _chk(count, torch.int32, "count")
+    if not torch.is_tensor(vertices) or not vertices.is_contiguous() or vertices.element_size() not in (4, 8):
+        raise TypeError("vertices: expected a contiguous tensor of a 4- or 8-byte dtype")
+    nf, nv, dev = faces.shape[0], vertices.shape[0], vertices.device
+    if count.shape[0] != nv:
+        raise ValueError("count: expected one entry per vertex")
+    if nv == 0:
+        return vertices[:0], faces[:0], torch.zeros(0, dtype=torch.bool, device=dev)
+    L = _lib.lib()
+    vkeep = torch.empty(nv, dtype=torch.uint8, device=dev)
+    fkeep = torch.empty(nf, dtype=torch.uint8, device=dev)
+    _lib.check(L.surf_dtu_clean_keep(_p(count), nv, _p(faces) if nf else None, nf, int(minimal_vis), _p(vkeep),
+                                     _p(fkeep) if nf else None, _stream()), "surf_dtu_clean_keep")
+    vscan = torch.cumsum(vkeep, 0, dtype=torch.int64)
+    fscan = torch.cumsum(fkeep, 0, dtype=torch.int64)
+    n_v, n_f = (int(x) for x in torch.stack([vscan[-1], fscan[-1] if nf else torch.zeros_like(vscan[-1])]).tolist())
+    out_v = torch.empty(n_v, 3, dtype=vertices.dtype, device=dev)
+    out_f = torch.empty(n_f, 3, dtype=torch.int32, device=dev)
+    if n_v:
+        _lib.check(L.surf_clean_compact_rows(_p(vertices), vertices.element_size(), _p(vkeep), _p(vscan), nv, _p(out_v), _stream()),
+                   "surf_clean_compact_rows")
+    if n_f:
+        _lib.check(L.surf_clean_compact_faces(_p(faces), _p(fkeep), _p(fscan), _p(vscan), nf, nv, _p(out_f), _stream()),
+                   "surf_clean_compact_faces")
+    return out_v, out_f, vkeep.view(torch.bool)
+
+
+# ------------------------------------------------------------------------------------------------
 # per-scene fine-tuning (finetune_rays.hip): the ray batch of one view, made on the device
 # ------------------------------------------------------------------------------------------------
 
