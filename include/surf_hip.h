@@ -37,7 +37,7 @@ extern "C" {
 #define SURF_E_LIMIT (-2)    /* exceeds SURF_MAX_* */
 
 /* ABI version, bumped whenever a signature below changes.  Defined here once: surf_abi_version() returns it and the
- * host binding (surf_amd/_lib.py ABI_VERSION) refuses a library that reports a different number. */
+ * host binding (surf_amd/_lib.py, which reads it from this line) refuses a library that reports a different number. */
 #define SURF_ABI_VERSION 41
 int surf_abi_version(void);
 

@@ -2,9 +2,13 @@
 
 The library is the product path: there is no CPU fallback.  Importing this module without the
 built library raises; calling a kernel without a GPU fails inside HIP.
+
+The header is the only place a signature or the ABI version is written: both are parsed from it at import, and lib()
+makes every status-returning entry point raise SurfHipError on a non-zero status by itself.
 """
 import ctypes
 import os
+import re
 import subprocess
 
 import torch  # noqa: F401  (load PyTorch's HIP runtime first: one runtime per process, whichever import order the caller uses)
@@ -12,170 +16,45 @@ import torch  # noqa: F401  (load PyTorch's HIP runtime first: one runtime per p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SURF_HIP_LIB", os.path.join(_HERE, "libsurf_hip.so"))
 
-# must equal SURF_ABI_VERSION of include/surf_hip.h (tests/test_host_modules.py compares the two texts); lib() refuses a
-# library built from another header
-ABI_VERSION = 41
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "surf_hip.h"))
 
-c_f32p = ctypes.c_void_p
-c_ptr = ctypes.c_void_p
-c_i64 = ctypes.c_int64
-c_int = ctypes.c_int
-c_float = ctypes.c_float
+# every parameter spelling include/surf_hip.h uses; anything with a `*` is a pointer
+_CTYPES = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
+           "double": ctypes.c_double}
+_DECL_HEAD = re.compile(r"^[ \t]*(?:int|int64_t)\s+(surf_\w+)\s*\(", re.M)
+_DECL = re.compile(r"^[ \t]*(int|int64_t)\s+(surf_\w+)\s*\(([^()]*)\)\s*;", re.M)
+# `int` entry points whose result is a value (a count, a size, a yes/no), not a status: lib() gives them no errcheck
+VALUE_RETURNING = frozenset({"surf_abi_version", "surf_blend_raw_floats", "surf_blend_packed_floats",
+                             "surf_blend_backward_row_floats", "surf_spconv_wgrad_mfma_supported"})
 
-# name -> (restype, argtypes); mirrors include/surf_hip.h one to one
-SIGNATURES = {
-    "surf_abi_version": (c_int, []),
-    "surf_pack_texel4": (c_int, [c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
-    "surf_ray_setup": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr,
-                               c_int, c_ptr, c_float, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_sdf_packed_floats": (c_i64, []),
-    "surf_sdf_pack_weights": (c_int, [c_ptr, c_ptr, c_ptr]),
-    "surf_sdf_scratch_bytes": (c_i64, [c_i64]),
-    "surf_sdf_mlp": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_sdf_bf16_packed_bytes": (c_i64, []),
-    "surf_sdf_bf16_scratch_bytes": (c_i64, [c_i64]),
-    "surf_sdf_pack_weights_bf16": (c_int, [c_ptr, c_ptr, c_ptr]),
-    "surf_sdf_mlp_bf16x3": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_sdf_mlp_bf16x3_dn": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_sdf_lattice_bf16x3": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_float, c_ptr]),
-    "surf_sdf_lattice_f16x2": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_float, c_ptr]),
-    "surf_sdf_bricks_bf16x3": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_float, c_ptr]),
-    "surf_sdf_bricks_f16x2": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_float, c_ptr]),
-    "surf_sdf_mlp_f16x2_dn": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_blend_split_dn": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_int,
-                                    c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_sdf_f16_packed_bytes": (c_i64, []),
-    "surf_sdf_f16_scratch_bytes": (c_i64, [c_i64]),
-    "surf_sdf_pack_weights_f16": (c_int, [c_ptr, c_ptr, c_ptr]),
-    "surf_sdf_mlp_f16x2": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_ptloss_terms": (c_int, [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_composite_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_float, c_float, c_ptr,
-                                        c_ptr, c_ptr, c_float, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_composite_backward_s": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_float, c_float, c_ptr,
-                                          c_ptr, c_ptr, c_float, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_sdf_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_blend_backward_row_floats": (c_int, []),
-    "surf_blend_backward": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_colgram_workspace_floats": (c_i64, [c_i64, c_int, c_int]),
-    "surf_colgram": (c_int, [c_ptr, c_int, c_int, c_ptr, c_int, c_int, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr]),
-    "surf_colgram_p": (c_int, [c_ptr, c_int, c_int, c_ptr, c_int, c_int, c_i64, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr]),
-    "surf_patch_warp_tangent": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_lncc_jvp": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr]),
-    "surf_crossing_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_lncc": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_ptr, c_ptr]),
-    "surf_lncc_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr]),
-    "surf_sdf_smooth_packed_floats": (c_i64, []),
-    "surf_sdf_smooth_pack_weights": (c_int, [c_ptr, c_ptr, c_ptr]),
-    "surf_sdf_smooth": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_blend_raw_floats": (c_int, []),
-    "surf_blend_packed_floats": (c_int, []),
-    "surf_blend_pack_weights": (c_int, [c_ptr, c_ptr]),
-    "surf_blend": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
-                           c_ptr, c_ptr]),
-    "surf_blend_split_packed_bytes": (c_i64, [c_int]),
-    "surf_blend_pack_weights_split": (c_int, [c_ptr, c_ptr, c_int]),
-    "surf_blend_split_scratch_bytes": (c_i64, [c_i64, c_int]),
-    "surf_blend_split": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_int,
-                                 c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_mc_classify": (c_int, [c_ptr, c_int, c_int, c_int, ctypes.c_double, c_ptr, c_ptr]),
-    "surf_mc_workspace_ints": (c_i64, [c_i64]),
-    "surf_mc_count": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
-    "surf_mc_emit": (c_int, [c_ptr, c_int, c_int, c_int, ctypes.c_double, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_band_table_size": (c_i64, [c_int]),
-    "surf_band_screen": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, ctypes.c_double, ctypes.c_double, c_ptr, c_ptr]),
-    "surf_band_promote": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr]),
-    "surf_band_assign": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_band_clear": (c_int, [c_ptr, c_i64, c_ptr, c_ptr]),
-    "surf_band_grow": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, ctypes.c_double, c_ptr, c_ptr]),
-    "surf_band_points": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr]),
-    "surf_band_classify": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, ctypes.c_double, c_ptr, c_ptr]),
-    "surf_band_keys": (c_int, [c_ptr, c_i64, c_ptr, c_int, c_ptr, c_ptr]),
-    "surf_band_rank": (c_int, [c_ptr, c_i64, c_ptr, c_int, c_ptr, c_ptr]),
-    "surf_band_emit": (c_int, [c_ptr, c_ptr, c_int, ctypes.c_double, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_raster_first_hit": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
-    "surf_dtu_sample_count": (c_int, [c_ptr, c_ptr, c_i64, ctypes.c_double, c_ptr, c_ptr]),
-    "surf_dtu_sample_write": (c_int, [c_ptr, c_ptr, c_i64, ctypes.c_double, c_ptr, c_ptr, c_ptr]),
-    "surf_dtu_cell_keys": (c_int, [c_ptr, c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i64, c_i64, c_i64, c_ptr, c_ptr]),
-    "surf_dtu_thin_round": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, ctypes.c_double, c_ptr, c_ptr, c_ptr]),
-    "surf_dtu_nearest": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i64, c_i64, c_i64, ctypes.c_double, c_ptr, c_ptr]),
-    "surf_clean_dilate": (c_int, [c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
-    "surf_clean_hull_count": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr]),
-    "surf_clean_face_keep": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr]),
-    "surf_clean_mark_visible": (c_int, [c_ptr, c_int, c_int, c_ptr, c_int, c_int, c_int, c_i64, c_ptr, c_ptr]),
-    "surf_clean_components_slots": (c_i64, [c_i64]),
-    "surf_clean_components": (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_clean_mark_used": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
-    "surf_clean_compact_faces": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
-    "surf_clean_compact_rows": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
-    "surf_dtu_clean_dilate": (c_int, [c_ptr, c_int, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr]),
-    "surf_dtu_clean_points_in_masks": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr]),
-    "surf_dtu_clean_keep": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr]),
-    "surf_finetune_rays": (c_int, [c_ptr, c_ptr, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_finetune_gather_pts": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr]),
-    "surf_vertex_points": (c_int, [c_ptr, c_int, c_i64, c_ptr, c_ptr, c_ptr]),
-    "surf_vertex_finish": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
-    "surf_composite": (c_int, [c_ptr] * 9 + [c_int, c_int, c_float, c_float] + [c_ptr] * 13),
-    "surf_upsample_bilinear_t4": (c_int, [c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
-    "surf_surface_points": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
-    "surf_patch_warp": (c_int, [c_ptr, c_ptr, c_int, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr]),
-    "surf_upsample_filter": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_float, c_ptr, c_ptr]),
-    "surf_costvol": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
-                             c_ptr]),
-    "surf_compact_workspace_ints": (c_i64, [c_i64]),
-    "surf_compact": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_gather_rows": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
-    "surf_compose_index": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
-    "surf_densify": (c_int, [c_ptr, c_ptr, c_int, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_spconv": (c_int, [c_ptr, c_int, c_ptr, c_int, c_ptr, c_i64, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_spconv_rows16": (c_int, [c_ptr, c_int, c_ptr, c_int, c_ptr, c_i64, c_int, c_ptr, c_int, c_ptr, c_ptr]),
-    "surf_rows_to_bf16": (c_int, [c_ptr, c_i64, c_ptr, c_ptr]),
-    "surf_bn_relu_apply16": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_bn_relu_backward16": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_bn_workspace_bytes": (c_i64, [c_int]),
-    "surf_bn_train_affine": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_ptr, ctypes.c_float, ctypes.c_float, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_matching_depth_backward": (c_int, [c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr,
-                                              c_int, c_ptr, ctypes.c_float, ctypes.c_float, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr,
-                                              c_ptr]),
-    "surf_densify_backward": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr]),
-    "surf_scatter_rows_add": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
-    "surf_costvol_backward_workspace_floats": (c_i64, [c_i64, c_int, c_int, c_int]),
-    "surf_costvol_backward_workspace_floats_for": (c_i64, [c_i64, c_int, c_ptr]),
-    "surf_costvol_backward": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_conv3x3_wgrad_workspace_floats": (c_i64, [c_int, c_int, c_int, c_int, c_int]),
-    "surf_conv3x3_wgrad": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr]),
-    "surf_conv3x3_wgrad_p": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_int, c_ptr]),
-    "surf_ptloss_backward": (c_int, [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_sdf_smooth_backward": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_bn_relu_backward": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_inorm_backward_workspace_bytes": (c_i64, [c_int, c_int]),
-    "surf_inorm_relu_backward": (c_int, [c_ptr, c_ptr, c_int, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_bn_relu_apply": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_spconv_wgrad": (c_int, [c_ptr, c_int, c_ptr, c_int, c_ptr, c_i64, c_int, c_ptr, c_int, c_ptr, c_ptr]),
-    "surf_spconv_wgrad_mfma_supported": (c_int, [c_int, c_int]),
-    "surf_spconv_wgrad_mfma": (c_int, [c_ptr, c_int, c_ptr, c_int, c_ptr, c_i64, c_int, c_ptr, c_int, c_ptr, c_ptr]),
-    "surf_spconv_packed_bytes": (c_i64, [c_int, c_int]),
-    "surf_spconv_pack_weights": (c_int, [c_ptr, c_int, c_int, c_ptr, c_ptr]),
-    "surf_spconv_mfma": (c_int, [c_ptr, c_int, c_ptr, c_int, c_ptr, c_i64, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr]),
-    "surf_coords_bbox": (c_int, [c_ptr, c_i64, c_ptr, c_ptr]),
-    "surf_mark_down_sites": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_ptr, c_int, c_ptr]),
-    "surf_sites_from_keys": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr]),
-    "surf_table_from_coords": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_ptr]),
-    "surf_row_linear8": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
-    "surf_conv3x3": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
-    "surf_conv3x3_p": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_int, c_ptr, c_int, c_ptr]),
-    "surf_deconv3x3_s2": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
-    "surf_deconv3x3_s2_p": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr, c_int, c_ptr]),
-    "surf_inorm_workspace_doubles": (c_i64, [c_int, c_int, c_int, c_int]),
-    "surf_inorm_relu": (c_int, [c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_inorm_relu_out": (c_int, [c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_occupied_any": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_int, c_ptr, c_ptr]),
-    "surf_masked_l1_workspace_bytes": (c_i64, []),
-    "surf_masked_l1": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_masked_l1_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_weight_norm_backward": (c_int, [c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "surf_matching_depth": (c_int, [c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr,
-                                    c_ptr, c_int, c_ptr, c_float, c_float, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-}
+
+def parse_header(text):
+    """The text of a C header -> {name: (restype, argtypes)} of its `int|int64_t surf_*(...);` declarations.  A parameter type
+    outside _CTYPES, or a declaration that only begins like one, raises with the function's name: nothing is guessed."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", "", text, flags=re.S)
+    sigs = {}
+    for res, name, params in _DECL.findall(text):
+        args = []
+        for param in ([] if params.strip() == "void" else params.split(",")):
+            ctype = ctypes.c_void_p if "*" in param else _CTYPES.get(" ".join(param.split()[:-1]))   # the type without the name
+            if ctype is None:
+                raise ValueError(f"{name}: no ctypes type for the parameter `{param.strip()}`")
+            args.append(ctype)
+        sigs[name] = (_CTYPES[res], args)
+    partial = [name for name in _DECL_HEAD.findall(text) if name not in sigs]
+    if partial:
+        raise ValueError(f"{', '.join(partial)}: declaration not understood")
+    return sigs
+
+
+try:
+    with open(HEADER_PATH) as _f:
+        _header = _f.read()
+except OSError as e:
+    raise RuntimeError(f"{HEADER_PATH}: the C header the binding is derived from cannot be read ({e.strerror})") from None
+# name -> (restype, argtypes), and the version lib() insists on: include/surf_hip.h is the only place either is written
+SIGNATURES = parse_header(_header)
+ABI_VERSION = int(re.search(r"^#define\s+SURF_ABI_VERSION\s+(\d+)", _header, re.M).group(1))
 
 _lib = None
 
@@ -201,13 +80,13 @@ def lib():
         cand = ctypes.CDLL(LIB_PATH)
         rebuild = "rebuild with surf_amd/csrc/build.sh (or __graft_entry__.build())"
         try:                                  # the version first: a stale library lacks newer symbols and would otherwise
-            cand.surf_abi_version.restype = c_int         # die with a bare AttributeError in the binding loop below
+            cand.surf_abi_version.restype = ctypes.c_int         # die with a bare AttributeError in the binding loop below
             cand.surf_abi_version.argtypes = []
             got = cand.surf_abi_version()
         except AttributeError:
             raise RuntimeError(f"{LIB_PATH} exports no surf_abi_version: not a surf_hip library; {rebuild}") from None
         if got != ABI_VERSION:
-            raise RuntimeError(f"{LIB_PATH} reports ABI version {got}, this binding is written for {ABI_VERSION}: {rebuild}")
+            raise RuntimeError(f"{LIB_PATH} reports ABI version {got}, include/surf_hip.h declares {ABI_VERSION}: {rebuild}")
         for name, (res, args) in SIGNATURES.items():
             try:
                 fn = getattr(cand, name)
@@ -215,6 +94,8 @@ def lib():
                 raise RuntimeError(f"{LIB_PATH} (ABI {got}) lacks {name}, which include/surf_hip.h declares: {rebuild}") from None
             fn.restype = res
             fn.argtypes = args
+            if res is ctypes.c_int and name not in VALUE_RETURNING:
+                fn.errcheck = _raise_on_status
         _lib = cand                           # cached only when fully bound
     return _lib
 
@@ -227,3 +108,12 @@ def check(code, what):
     if code != 0:
         kind = {-1: "invalid argument", -2: "exceeds a SURF_MAX_* limit"}.get(code, f"hipError {code}")
         raise SurfHipError(f"{what}: {kind}")
+
+
+def _raise_on_status(code, fn, args):
+    """errcheck of the status-returning entry points: 0 passes through, anything else raises with the entry point's name and
+    the scalar arguments of the call (sizes, strides, modes: what tells one launch of a kernel from another)."""
+    if code != 0:
+        scalars = ", ".join(repr(getattr(a, "value", a)) for t, a in zip(fn.argtypes, args) if t is not ctypes.c_void_p)
+        check(code, f"{fn.__name__}({scalars})")
+    return code

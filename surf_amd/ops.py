@@ -232,6 +232,11 @@ def _np_ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _host_ptr_array(arrays):
+    """The `const float* const*` of host arrays (the seven weight matrices / biases of an SDF network)."""
+    return (ctypes.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
+
+
 # ------------------------------------------------------------------------------------------------
 # layout helpers
 # ------------------------------------------------------------------------------------------------
@@ -242,7 +247,7 @@ def pack_texel4(x):
     _chk(x, torch.float32, "x")
     n, C, H, W = x.shape
     out = torch.empty(n, H, W, 4, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().surf_pack_texel4(_p(x), n, C, H, W, _p(out), _stream()), "surf_pack_texel4")
+    _lib.lib().surf_pack_texel4(_p(x), n, C, H, W, _p(out), _stream())
     return out
 
 
@@ -296,9 +301,8 @@ def sdf_pack_weights_host(layers):
     bs = [_host_f32(b) for _, b in layers]
     L = _lib.lib()
     out = np.zeros(L.surf_sdf_packed_floats(), dtype=np.float32)
-    wp = (ctypes.c_void_p * 7)(*[w.ctypes.data for w in Ws])
-    bp = (ctypes.c_void_p * 7)(*[b.ctypes.data for b in bs])
-    _lib.check(L.surf_sdf_pack_weights(wp, bp, _np_ptr(out)), "surf_sdf_pack_weights")
+    wp, bp = _host_ptr_array(Ws), _host_ptr_array(bs)
+    L.surf_sdf_pack_weights(wp, bp, _np_ptr(out))
     return out
 
 
@@ -320,9 +324,8 @@ def sdf_pack_weights_split_host(layers, precision):
     bs = [_host_f32(b) for _, b in layers]
     L = _lib.lib()
     out = np.zeros(getattr(L, f"surf_sdf_{infix}_packed_bytes")(), dtype=np.uint8)
-    wp = (ctypes.c_void_p * 7)(*[w.ctypes.data for w in Ws])
-    bp = (ctypes.c_void_p * 7)(*[b.ctypes.data for b in bs])
-    _lib.check(getattr(L, f"surf_sdf_pack_weights_{infix}")(wp, bp, _np_ptr(out)), f"surf_sdf_pack_weights_{infix}")
+    wp, bp = _host_ptr_array(Ws), _host_ptr_array(bs)
+    getattr(L, f"surf_sdf_pack_weights_{infix}")(wp, bp, _np_ptr(out))
     return out
 
 
@@ -362,8 +365,7 @@ def blend_pack_weights_host(raw):
     if raw.size != L.surf_blend_raw_floats():
         raise NotImplementedError("colour network shape differs from the shipped BlendingNetwork(d_feature=16)")
     out = np.zeros(L.surf_blend_packed_floats(), dtype=np.float32)
-    _lib.check(L.surf_blend_pack_weights(_np_ptr(np.ascontiguousarray(raw, dtype=np.float32)), _np_ptr(out)),
-               "surf_blend_pack_weights")
+    L.surf_blend_pack_weights(_np_ptr(np.ascontiguousarray(raw, dtype=np.float32)), _np_ptr(out))
     return out
 
 
@@ -374,8 +376,7 @@ def blend_pack_weights_split_host(raw, precision):
         raise NotImplementedError("colour network shape differs from the shipped BlendingNetwork(d_feature=16)")
     pid = _BLEND_ID[precision]
     out = np.zeros(L.surf_blend_split_packed_bytes(pid), dtype=np.uint8)
-    _lib.check(L.surf_blend_pack_weights_split(_np_ptr(np.ascontiguousarray(raw, dtype=np.float32)), _np_ptr(out), pid),
-               "surf_blend_pack_weights_split")
+    L.surf_blend_pack_weights_split(_np_ptr(np.ascontiguousarray(raw, dtype=np.float32)), _np_ptr(out), pid)
     return out
 
 
@@ -496,27 +497,29 @@ def ray_setup(rays_o, rays_d, near, far, mvol, volumes, n_samples, sample_ranges
         out["z_vals"] = torch.empty(R, S, dtype=torch.float32, device=dev)
     ns = (ctypes.c_int * len(n_samples))(*[int(n) for n in n_samples])
     rg = (ctypes.c_float * len(sample_ranges))(*[float(r) for r in sample_ranges])
-    rc = _lib.lib().surf_ray_setup(_p(rays_o), _p(rays_d), _p(near), _p(far), R, _p(mvol), int(mvol.shape[-1]),
-                                   _p(lin_depth), int(n_depth), _p(lin_s), ns, rg, len(n_samples), _p(jitter),
-                                   ctypes.c_float(2.0 / n_samples[0]), volumes._tp, volumes._dp, volumes.n,
-                                   _p(out.get("z_vals")), _p(out["mid_z"]), _p(out["dists"]), _p(out["pts"]),
-                                   _p(out["vmask"]), _stream())
-    _lib.check(rc, "surf_ray_setup")
+    _lib.lib().surf_ray_setup(_p(rays_o), _p(rays_d), _p(near), _p(far), R, _p(mvol), int(mvol.shape[-1]),
+                              _p(lin_depth), int(n_depth), _p(lin_s), ns, rg, len(n_samples), _p(jitter),
+                              float(2.0 / n_samples[0]), volumes._tp, volumes._dp, volumes.n,
+                              _p(out.get("z_vals")), _p(out["mid_z"]), _p(out["dists"]), _p(out["pts"]),
+                              _p(out["vmask"]), _stream())
     return out
 
 
 _scratch_cache = {}
 
 
-def _sdf_scratch(n, device, precision="f32"):
-    fn = "surf_sdf_scratch_bytes" if precision == "f32" else f"surf_sdf_{_SPLIT_ABI[precision]}_scratch_bytes"
-    need = getattr(_lib.lib(), fn)(int(n))
-    key = (device.index if device.index is not None else torch.cuda.current_device())
+def _scratch(user, need, device):
+    """A byte buffer of at least `need` bytes on `device`: one per user and device, replaced only by a larger one."""
+    key = (user, device.index if device.index is not None else torch.cuda.current_device())
     buf = _scratch_cache.get(key)
     if buf is None or buf.numel() < need:
-        buf = torch.empty(need, dtype=torch.uint8, device=device)
-        _scratch_cache[key] = buf
+        buf = _scratch_cache[key] = torch.empty(need, dtype=torch.uint8, device=device)
     return buf
+
+
+def _sdf_scratch(n, device, precision="f32"):
+    fn = "surf_sdf_scratch_bytes" if precision == "f32" else f"surf_sdf_{_SPLIT_ABI[precision]}_scratch_bytes"
+    return _scratch("sdf", getattr(_lib.lib(), fn)(int(n)), device)
 
 
 def sdf_mlp(pts, volumes, packed, mask=None, want_grad=True, compact_active=True, active_idx=None, active_count=None):
@@ -553,14 +556,12 @@ def sdf_mlp(pts, volumes, packed, mask=None, want_grad=True, compact_active=True
             raise ValueError("active_count needs active_idx and one of the split kernels (bf16x3 / f16x2)")
         _chk(active_count, torch.int32, "active_count")
         fn = getattr(_lib.lib(), name + "_dn")
-        rc = fn(_p(pts), _p(idx), n_eval, _p(active_count), volumes._vp, volumes._tp, volumes._dp, volumes.n, _p(packed), _p(sdf),
-                _p(grad), _p(scratch), _stream())
-        _lib.check(rc, name + "_dn")
+        fn(_p(pts), _p(idx), n_eval, _p(active_count), volumes._vp, volumes._tp, volumes._dp, volumes.n, _p(packed), _p(sdf),
+           _p(grad), _p(scratch), _stream())
         return sdf, grad
     fn = getattr(_lib.lib(), name)
-    rc = fn(_p(pts), _p(None if idx is not None else mask), _p(idx), n_eval, volumes._vp, volumes._tp, volumes._dp, volumes.n,
-            _p(packed), _p(sdf), _p(grad), _p(scratch), _stream())
-    _lib.check(rc, name)
+    fn(_p(pts), _p(None if idx is not None else mask), _p(idx), n_eval, volumes._vp, volumes._tp, volumes._dp, volumes.n,
+       _p(packed), _p(sdf), _p(grad), _p(scratch), _stream())
     return sdf, grad
 
 
@@ -577,9 +578,8 @@ def sdf_lattice(axes, volumes, packed, out, x0, nx, sign=-1.0):
     ny, nz = int(axes[1].shape[0]), int(axes[2].shape[0])
     assert tuple(out.shape) == (int(axes[0].shape[0]), ny, nz) and 0 <= x0 and x0 + nx <= out.shape[0]
     name = f"surf_sdf_lattice_{precision}"
-    rc = getattr(_lib.lib(), name)(_p(axes[0][x0:]), _p(axes[1]), _p(axes[2]), int(nx), ny, nz, volumes._vp, volumes._tp, volumes._dp,
-                                   volumes.n, _p(packed), _p(out[x0:]), ctypes.c_float(sign), _stream())
-    _lib.check(rc, name)
+    getattr(_lib.lib(), name)(_p(axes[0][x0:]), _p(axes[1]), _p(axes[2]), int(nx), ny, nz, volumes._vp, volumes._tp, volumes._dp,
+                              volumes.n, _p(packed), _p(out[x0:]), float(sign), _stream())
 
 
 def sdf_smooth_pack_weights_host(layers):
@@ -589,9 +589,8 @@ def sdf_smooth_pack_weights_host(layers):
     bs = [_host_f32(b) for _, b in layers]
     L = _lib.lib()
     out = np.zeros(L.surf_sdf_smooth_packed_floats(), dtype=np.float32)
-    wp = (ctypes.c_void_p * 7)(*[w.ctypes.data for w in Ws])
-    bp = (ctypes.c_void_p * 7)(*[b.ctypes.data for b in bs])
-    _lib.check(L.surf_sdf_smooth_pack_weights(wp, bp, _np_ptr(out)), "surf_sdf_smooth_pack_weights")
+    wp, bp = _host_ptr_array(Ws), _host_ptr_array(bs)
+    L.surf_sdf_smooth_pack_weights(wp, bp, _np_ptr(out))
     return out
 
 
@@ -615,9 +614,8 @@ def sdf_smooth(pts, volumes, packed, active_idx=None, want_grad=False):
         smooth = torch.empty(n, 3, dtype=torch.float32, device=pts.device)
         grad = torch.empty(n, 3, dtype=torch.float32, device=pts.device) if want_grad else None
         n_eval = n
-    rc = _lib.lib().surf_sdf_smooth(_p(pts), _p(active_idx), n_eval, volumes._vp, volumes._tp, volumes._dp, volumes.n,
-                                    _p(packed), _p(grad), _p(smooth), _stream())
-    _lib.check(rc, "surf_sdf_smooth")
+    _lib.lib().surf_sdf_smooth(_p(pts), _p(active_idx), n_eval, volumes._vp, volumes._tp, volumes._dp, volumes.n,
+                               _p(packed), _p(grad), _p(smooth), _stream())
     return smooth, grad
 
 
@@ -639,10 +637,9 @@ def sdf_backward(pts, ybar, gbar, volumes, packed, want_dvols=True, dvols=None):
     else:
         dvols = [torch.zeros_like(v) for v in volumes.vols] if want_dvols else None
     with _timed("sdf_bwd", n):
-        rc = _lib.lib().surf_sdf_backward(_p(pts), _p(ybar), _p(gbar), n, volumes._vp, volumes._tp, volumes._dp, volumes.n,
-                                          _ptr_array(dvols) if dvols is not None else None, _p(packed), _p(in_v), _p(in_d), _p(tb),
-                                          _p(tdb), _stream())
-    _lib.check(rc, "surf_sdf_backward")
+        _lib.lib().surf_sdf_backward(_p(pts), _p(ybar), _p(gbar), n, volumes._vp, volumes._tp, volumes._dp, volumes.n,
+                                     _ptr_array(dvols) if dvols is not None else None, _p(packed), _p(in_v), _p(in_d), _p(tb),
+                                     _p(tdb), _stream())
     shapes = [(128, 27), (128, 156), (101, 156), (128, 156), (128, 156), (128, 156), (129, 156)]
     dW, db = [], []
     for l in range(6):
@@ -676,9 +673,8 @@ def sdf_smooth_backward(pts, sbar, volumes, packed, want_dvols=True, dvols=None)
     else:
         dvols = [torch.zeros_like(v) for v in volumes.vols] if want_dvols else None
     with _timed("sdf_smooth_bwd", n):
-        rc = _lib.lib().surf_sdf_smooth_backward(_p(pts), _p(sbar), n, volumes._vp, volumes._tp, volumes._dp, volumes.n,
-                                                 _ptr_array(dvols) if dvols is not None else None, _p(packed), _p(xin), _p(ab), _stream())
-    _lib.check(rc, "surf_sdf_smooth_backward")
+        _lib.lib().surf_sdf_smooth_backward(_p(pts), _p(sbar), n, volumes._vp, volumes._tp, volumes._dp, volumes.n,
+                                            _ptr_array(dvols) if dvols is not None else None, _p(packed), _p(xin), _p(ab), _stream())
     shapes = [(128, 27), (128, 156), (101, 156), (128, 156), (128, 156), (128, 156), (129, 156)]
     dW, db = [], []
     for l in range(6):
@@ -713,7 +709,7 @@ def rows_to_bf16(x):
     _chk(x, torch.float32, "x")
     out = torch.empty(x.shape, dtype=torch.int16, device=x.device)
     if x.numel():
-        _lib.check(_lib.lib().surf_rows_to_bf16(_p(x), x.numel(), _p(out), _stream()), "surf_rows_to_bf16")
+        _lib.lib().surf_rows_to_bf16(_p(x), x.numel(), _p(out), _stream())
     return out
 
 
@@ -766,9 +762,8 @@ def colgram(A, X, with_sum=False, out=None, precision=None):
         return out if acc else out.zero_()
     ws = torch.empty(_lib.lib().surf_colgram_workspace_floats(rows, M, N), dtype=torch.float32, device=A.device)
     with _timed("colgram", rows * M * (N + (1 if with_sum else 0))):
-        rc = _lib.lib().surf_colgram_p(_p(A), int(A.stride(0)), M, _p(X), int(X.stride(0)), N, rows, int(with_sum), int(acc),
-                                       int(colgram_precision if precision is None else precision), _p(ws), _p(out), _stream())
-    _lib.check(rc, "surf_colgram_p")
+        _lib.lib().surf_colgram_p(_p(A), int(A.stride(0)), M, _p(X), int(X.stride(0)), N, rows, int(with_sum), int(acc),
+                                  int(colgram_precision if precision is None else precision), _p(ws), _p(out), _stream())
     return out
 
 
@@ -799,11 +794,10 @@ def blend_backward(pts, active_idx, gcolor, feats_t4, imgs_t4, cams, raw_weights
         hw = (ctypes.c_int * 8)(*[int(v) for f in feats_t4 for v in f.shape[1:3]])
         intr16 = np.ascontiguousarray(cams.intrs.reshape(cams.nv, -1))
         with _timed("blend_bwd", n * V):
-            rc = _lib.lib().surf_blend_backward(_p(pts), _p(active_idx), n, _p(gcolor), _ptr_array(list(feats_t4)), hw, _p(imgs_t4),
-                                                cams.nv, _np_ptr(intr16), _np_ptr(cams.w2c), _np_ptr(cams.c2w), _p(raw_weights),
-                                                _p(rows), _p(ds), _p(color),
-                                                None if gfeats_t4 is None else _ptr_array(list(gfeats_t4)), _stream())
-        _lib.check(rc, "surf_blend_backward")
+            _lib.lib().surf_blend_backward(_p(pts), _p(active_idx), n, _p(gcolor), _ptr_array(list(feats_t4)), hw, _p(imgs_t4),
+                                           cams.nv, _np_ptr(intr16), _np_ptr(cams.w2c), _np_ptr(cams.c2w), _p(raw_weights),
+                                           _p(rows), _p(ds), _p(color),
+                                           None if gfeats_t4 is None else _ptr_array(list(gfeats_t4)), _stream())
     flat = rows[:n].reshape(-1, ROW)
     for name, cin, cout, c_in, c_ad in _BLEND_LAYERS:
         g = colgram(flat[:, c_ad:c_ad + cout], flat[:, c_in:c_in + cin], with_sum=True)
@@ -852,26 +846,20 @@ def blend(pts, feats_t4, imgs_t4, cams, packed, mask=None, compact_active=True, 
     if precision == "f32" and active_count is not None:
         raise ValueError("active_count needs one of the split blend kernels")
     if precision == "f32":
-        rc = _lib.lib().surf_blend(_p(pts), _p(None if idx is not None else mask), _p(idx), n_eval, fp, hw, len(feats_t4),
-                                   _p(imgs_t4), cams.nv, _np_ptr(cams.intrs), _np_ptr(cams.w2c), _np_ptr(cams.c2w), _p(packed),
-                                   _p(color), _p(nvalid), _stream())
+        _lib.lib().surf_blend(_p(pts), _p(None if idx is not None else mask), _p(idx), n_eval, fp, hw, len(feats_t4),
+                              _p(imgs_t4), cams.nv, _np_ptr(cams.intrs), _np_ptr(cams.w2c), _np_ptr(cams.c2w), _p(packed),
+                              _p(color), _p(nvalid), _stream())
     else:
-        need = _lib.lib().surf_blend_split_scratch_bytes(int(n_eval), cams.nv)
-        key = ("blend", dev.index if dev.index is not None else torch.cuda.current_device())
-        scratch = _scratch_cache.get(key)
-        if scratch is None or scratch.numel() < need:
-            scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-            _scratch_cache[key] = scratch
+        scratch = _scratch("blend", _lib.lib().surf_blend_split_scratch_bytes(int(n_eval), cams.nv), dev)
         if active_count is not None:           # the count stays on the device (compact_counted)
             _chk(active_count, torch.int32, "active_count")
-            rc = _lib.lib().surf_blend_split_dn(_p(pts), _p(idx), n_eval, _p(active_count), fp, hw, len(feats_t4), _p(imgs_t4),
-                                                cams.nv, _np_ptr(cams.intrs), _np_ptr(cams.w2c), _np_ptr(cams.c2w), _p(packed),
-                                                _BLEND_ID[precision], _p(color), _p(nvalid), _p(scratch), _stream())
+            _lib.lib().surf_blend_split_dn(_p(pts), _p(idx), n_eval, _p(active_count), fp, hw, len(feats_t4), _p(imgs_t4),
+                                           cams.nv, _np_ptr(cams.intrs), _np_ptr(cams.w2c), _np_ptr(cams.c2w), _p(packed),
+                                           _BLEND_ID[precision], _p(color), _p(nvalid), _p(scratch), _stream())
         else:
-            rc = _lib.lib().surf_blend_split(_p(pts), _p(None if idx is not None else mask), _p(idx), n_eval, fp, hw, len(feats_t4),
-                                             _p(imgs_t4), cams.nv, _np_ptr(cams.intrs), _np_ptr(cams.w2c), _np_ptr(cams.c2w),
-                                             _p(packed), _BLEND_ID[precision], _p(color), _p(nvalid), _p(scratch), _stream())
-    _lib.check(rc, "surf_blend" if precision == "f32" else f"surf_blend_split({precision})")
+            _lib.lib().surf_blend_split(_p(pts), _p(None if idx is not None else mask), _p(idx), n_eval, fp, hw, len(feats_t4),
+                                        _p(imgs_t4), cams.nv, _np_ptr(cams.intrs), _np_ptr(cams.w2c), _np_ptr(cams.c2w),
+                                        _p(packed), _BLEND_ID[precision], _p(color), _p(nvalid), _p(scratch), _stream())
     return color, nvalid
 
 
@@ -892,14 +880,13 @@ def composite(sdf, grad, color, n_valid, setup, rays_d, inv_s, cos_anneal_ratio,
         out["inside_sphere"] = torch.empty(R, S, **f32)
     if want_z0:
         out["z_sdf0"] = torch.empty(R, **f32)
-    rc = _lib.lib().surf_composite(_p(sdf), _p(grad), _p(color), _p(n_valid), _p(setup["mid_z"]), _p(setup["dists"]),
-                                   _p(setup["pts"]), _p(setup["vmask"]), _p(rays_d), R, S, ctypes.c_float(inv_s),
-                                   ctypes.c_float(cos_anneal_ratio), _np_ptr(cams.rot_ref), _p(out["color_fine"]),
-                                   _p(out["render_depth"]), _p(out["sdf_depth"]), _p(out["normal"]),
-                                   _p(out["normal_val"]), _p(out["valid_mask"]), _p(out["mid_inside_sphere"]),
-                                   _p(out.get("weights")), _p(out.get("inside_sphere")), _p(out["eik"]), _p(out.get("z_sdf0")),
-                                   _stream())
-    _lib.check(rc, "surf_composite")
+    _lib.lib().surf_composite(_p(sdf), _p(grad), _p(color), _p(n_valid), _p(setup["mid_z"]), _p(setup["dists"]),
+                              _p(setup["pts"]), _p(setup["vmask"]), _p(rays_d), R, S, float(inv_s),
+                              float(cos_anneal_ratio), _np_ptr(cams.rot_ref), _p(out["color_fine"]),
+                              _p(out["render_depth"]), _p(out["sdf_depth"]), _p(out["normal"]),
+                              _p(out["normal_val"]), _p(out["valid_mask"]), _p(out["mid_inside_sphere"]),
+                              _p(out.get("weights")), _p(out.get("inside_sphere")), _p(out["eik"]), _p(out.get("z_sdf0")),
+                              _stream())
     return out
 
 
@@ -917,12 +904,11 @@ def composite_backward(sdf, grad, color, setup, rays_d, inv_s, cos_anneal_ratio,
     d_is = torch.empty(R, dtype=torch.float32, device=dev)
     if eik_upstream is not None:        # dL/d gradient_error as a device scalar: multiplied in inside the kernel, never read back
         eik_upstream = _chk(eik_upstream.detach().reshape(1).float().contiguous(), torch.float32, "eik_upstream")
-    rc = _lib.lib().surf_composite_backward_s(_p(sdf), _p(grad), _p(color), _p(setup["mid_z"]), _p(setup["dists"]), _p(setup["pts"]),
-                                              _p(setup["vmask"]), _p(rays_d), R, S, ctypes.c_float(inv_s),
-                                              ctypes.c_float(cos_anneal_ratio), _np_ptr(cams.rot_ref), _p(g_color), _p(g_depth),
-                                              ctypes.c_float(float(eik_scale)), _p(eik_upstream), _p(d_sdf), _p(d_grad), _p(d_color),
-                                              _p(d_is), _stream())
-    _lib.check(rc, "surf_composite_backward_s")
+    _lib.lib().surf_composite_backward_s(_p(sdf), _p(grad), _p(color), _p(setup["mid_z"]), _p(setup["dists"]), _p(setup["pts"]),
+                                         _p(setup["vmask"]), _p(rays_d), R, S, float(inv_s),
+                                         float(cos_anneal_ratio), _np_ptr(cams.rot_ref), _p(g_color), _p(g_depth),
+                                         float(eik_scale), _p(eik_upstream), _p(d_sdf), _p(d_grad), _p(d_color),
+                                         _p(d_is), _stream())
     return d_sdf, d_grad, d_color, d_is.sum(dtype=torch.float64).float()
 
 
@@ -932,7 +918,7 @@ def upsample_bilinear_t4(x, H, W):
     n, h, w, c = x.shape
     assert c == 4
     out = torch.empty(n, H, W, 4, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().surf_upsample_bilinear_t4(_p(x), n, h, w, int(H), int(W), _p(out), _stream()), "surf_upsample_bilinear_t4")
+    _lib.lib().surf_upsample_bilinear_t4(_p(x), n, h, w, int(H), int(W), _p(out), _stream())
     return out
 
 
@@ -945,8 +931,7 @@ def surface_points(rays_o, rays_d, z_sdf0, z_vals):
     R = rays_o.shape[0]
     ws = torch.empty(1, dtype=torch.int32, device=rays_o.device)
     pts = torch.empty(R, 3, dtype=torch.float32, device=rays_o.device)
-    _lib.check(_lib.lib().surf_surface_points(_p(rays_o), _p(rays_d), _p(z_sdf0), R, _p(z_vals), z_vals.numel(), _p(ws), _p(pts),
-                                              _stream()), "surf_surface_points")
+    _lib.lib().surf_surface_points(_p(rays_o), _p(rays_d), _p(z_sdf0), R, _p(z_vals), z_vals.numel(), _p(ws), _p(pts), _stream())
     return pts
 
 
@@ -969,9 +954,8 @@ def patch_warp(pts, grads, maps_t4, cams, patch_size=11):
     P = patch_size * patch_size
     ref = torch.empty(1, R, P, 12, dtype=torch.float32, device=dev)
     src = torch.empty(nv - 1, R, P, 12, dtype=torch.float32, device=dev)
-    rc = _lib.lib().surf_patch_warp(_p(pts), _p(grads), R, _ptr_array(list(maps_t4)), nv, H, W, _np_ptr(K), _np_ptr(kinv),
-                                    _np_ptr(c2w), int(patch_size), _p(ref), _p(src), _stream())
-    _lib.check(rc, "surf_patch_warp")
+    _lib.lib().surf_patch_warp(_p(pts), _p(grads), R, _ptr_array(list(maps_t4)), nv, H, W, _np_ptr(K), _np_ptr(kinv),
+                               _np_ptr(c2w), int(patch_size), _p(ref), _p(src), _stream())
     return ref, src
 
 
@@ -989,9 +973,8 @@ def photometric_loss(depth, imgs_t4, mask_ref, cams, ref_idx=0, topk=2, return_w
     terms = torch.empty(H, W, 8, dtype=torch.float32, device=dev)
     intr16 = np.ascontiguousarray(cams.intrs.reshape(nv, -1))
     assert intr16.shape[1] == 16
-    rc = _lib.lib().surf_ptloss_terms(_p(imgs_t4), nv, H, W, _p(depth), _p(mask_ref), int(ref_idx), int(topk), _np_ptr(intr16),
-                                      _np_ptr(cams.c2w), _np_ptr(cams.w2c), _p(warp), _p(terms), _stream())
-    _lib.check(rc, "surf_ptloss_terms")
+    _lib.lib().surf_ptloss_terms(_p(imgs_t4), nv, H, W, _p(depth), _p(mask_ref), int(ref_idx), int(topk), _np_ptr(intr16),
+                                 _np_ptr(cams.c2w), _np_ptr(cams.w2c), _p(warp), _p(terms), _stream())
     t = terms.view(-1, 8).sum(dim=0, dtype=torch.float64)       # columns [l1 m, gx mx, gy my, ssim m | m, mx, my, m]
     loss = (t[:4] / (t[4:] + 1e-8)).sum().float()
     if return_state:
@@ -1012,16 +995,14 @@ def photometric_loss_backward(depth, imgs_t4, mask_ref, cams, ref_idx=0, topk=2,
     else:
         warp = torch.empty(nv - 1, H, W, 4, dtype=torch.float32, device=dev)
         terms = torch.empty(H, W, 8, dtype=torch.float32, device=dev)
-        rc = _lib.lib().surf_ptloss_terms(_p(imgs_t4), nv, H, W, _p(depth), _p(mask_ref), int(ref_idx), int(topk), _np_ptr(intr16),
-                                          _np_ptr(cams.c2w), _np_ptr(cams.w2c), _p(warp), _p(terms), _stream())
-        _lib.check(rc, "surf_ptloss_terms")
+        _lib.lib().surf_ptloss_terms(_p(imgs_t4), nv, H, W, _p(depth), _p(mask_ref), int(ref_idx), int(topk), _np_ptr(intr16),
+                                     _np_ptr(cams.c2w), _np_ptr(cams.w2c), _p(warp), _p(terms), _stream())
         t = terms.view(-1, 8).sum(dim=0, dtype=torch.float64)
     coef = (upstream / (t[4:] + 1e-8)).float().contiguous()
     g_warp = torch.empty_like(warp)
     g_depth = torch.empty(H, W, dtype=torch.float32, device=dev)
-    rc = _lib.lib().surf_ptloss_backward(_p(imgs_t4), nv, H, W, _p(depth), _p(mask_ref), int(ref_idx), int(topk), _np_ptr(intr16),
-                                         _np_ptr(cams.c2w), _np_ptr(cams.w2c), _p(warp), _p(coef), _p(g_warp), _p(g_depth), _stream())
-    _lib.check(rc, "surf_ptloss_backward")
+    _lib.lib().surf_ptloss_backward(_p(imgs_t4), nv, H, W, _p(depth), _p(mask_ref), int(ref_idx), int(topk), _np_ptr(intr16),
+                                    _np_ptr(cams.c2w), _np_ptr(cams.w2c), _p(warp), _p(coef), _p(g_warp), _p(g_depth), _stream())
     return g_depth
 
 
@@ -1036,10 +1017,9 @@ def patch_warp_tangent(pts, dirs, grads, maps_t4, cams, patch_size=11):
         cams.kinv_ref = np.ascontiguousarray(torch.inverse(torch.from_numpy(cams.intrs))[0, :3, :3].contiguous().numpy())
     ref, ref_t = (torch.empty(1, R, P, 12, dtype=torch.float32, device=dev) for _ in range(2))
     src, src_t = (torch.empty(nv - 1, R, P, 12, dtype=torch.float32, device=dev) for _ in range(2))
-    rc = _lib.lib().surf_patch_warp_tangent(_p(pts), _p(dirs), _p(grads), R, _ptr_array(list(maps_t4)), nv, H, W, _np_ptr(cams.intrs),
-                                            _np_ptr(cams.kinv_ref), _np_ptr(cams.c2w), int(patch_size), _p(ref), _p(src), _p(ref_t),
-                                            _p(src_t), _stream())
-    _lib.check(rc, "surf_patch_warp_tangent")
+    _lib.lib().surf_patch_warp_tangent(_p(pts), _p(dirs), _p(grads), R, _ptr_array(list(maps_t4)), nv, H, W, _np_ptr(cams.intrs),
+                                       _np_ptr(cams.kinv_ref), _np_ptr(cams.c2w), int(patch_size), _p(ref), _p(src), _p(ref_t),
+                                       _p(src_t), _stream())
     return ref, src, ref_t, src_t
 
 
@@ -1048,8 +1028,7 @@ def lncc_jvp(ref, src, ref_tan, src_tan):
     nsrc, R, P, C = src.shape
     ncc = torch.empty(R, 1, dtype=torch.float32, device=ref.device)
     d = torch.empty(R, dtype=torch.float32, device=ref.device)
-    rc = _lib.lib().surf_lncc_jvp(_p(ref), _p(src), _p(ref_tan), _p(src_tan), R, int(nsrc), int(P), int(C), _p(ncc), _p(d), _stream())
-    _lib.check(rc, "surf_lncc_jvp")
+    _lib.lib().surf_lncc_jvp(_p(ref), _p(src), _p(ref_tan), _p(src_tan), R, int(nsrc), int(P), int(C), _p(ncc), _p(d), _stream())
     return ncc, d
 
 
@@ -1057,9 +1036,8 @@ def crossing_backward(sdf, vmask, mid_z, zmax, g_z0, d_sdf):
     """d_sdf (R*S,) += g_z0 (R,) d z0 / d sdf at the first zero crossing of every ray (surf_crossing_backward); zmax: 0-d tensor."""
     R, S = mid_z.shape
     _chk(d_sdf, torch.float32, "d_sdf")
-    rc = _lib.lib().surf_crossing_backward(_p(sdf), _p(vmask), _p(mid_z), R, S, _p(zmax.reshape(1).float().contiguous()),
-                                           _p(g_z0.float().contiguous()), _p(d_sdf), _stream())
-    _lib.check(rc, "surf_crossing_backward")
+    _lib.lib().surf_crossing_backward(_p(sdf), _p(vmask), _p(mid_z), R, S, _p(zmax.reshape(1).float().contiguous()),
+                                      _p(g_z0.float().contiguous()), _p(d_sdf), _stream())
     return d_sdf
 
 
@@ -1071,8 +1049,7 @@ def lncc(ref_gray_val, sampled_gray_val):
     assert tuple(ref_gray_val.shape) == (1, R, P, C)
     out = torch.empty(R, 1, dtype=torch.float32, device=ref_gray_val.device)
     if R > 0:
-        _lib.check(_lib.lib().surf_lncc(_p(ref_gray_val), _p(sampled_gray_val), R, int(nsrc), int(P), int(C), _p(out), _stream()),
-                   "surf_lncc")
+        _lib.lib().surf_lncc(_p(ref_gray_val), _p(sampled_gray_val), R, int(nsrc), int(P), int(C), _p(out), _stream())
     return out
 
 
@@ -1085,8 +1062,8 @@ def lncc_backward(ref_gray_val, sampled_gray_val, g_ncc):
     assert g.shape[0] == R
     g_ref, g_src = torch.empty_like(ref_gray_val), torch.empty_like(sampled_gray_val)
     if R > 0:
-        _lib.check(_lib.lib().surf_lncc_backward(_p(ref_gray_val), _p(sampled_gray_val), _p(g), R, int(nsrc), int(P), int(C),
-                                                 _p(g_ref), _p(g_src), _stream()), "surf_lncc_backward")
+        _lib.lib().surf_lncc_backward(_p(ref_gray_val), _p(sampled_gray_val), _p(g), R, int(nsrc), int(P), int(C),
+                                      _p(g_ref), _p(g_src), _stream())
     return g_ref, g_src
 
 
@@ -1111,9 +1088,8 @@ def upsample_filter(parents, D, depths, cams, depth_range):
     _chk(depths, torch.float32, "depths")
     nv, H, W = depths.shape
     flags = torch.empty(parents.shape[0] * 8, dtype=torch.uint8, device=parents.device)
-    rc = _lib.lib().surf_upsample_filter(_p(parents), parents.shape[0], int(D), _p(depths), nv, H, W, _np_ptr(cams.intrs),
-                                         _np_ptr(cams.w2c), ctypes.c_float(float(depth_range)), _p(flags), _stream())
-    _lib.check(rc, "surf_upsample_filter")
+    _lib.lib().surf_upsample_filter(_p(parents), parents.shape[0], int(D), _p(depths), nv, H, W, _np_ptr(cams.intrs),
+                                    _np_ptr(cams.w2c), float(depth_range), _p(flags), _stream())
     return flags
 
 
@@ -1133,9 +1109,8 @@ def costvol(feats_t4_c2f, stage, D, cams, agg, parents=None, idx=None):
     hw = (ctypes.c_int * 8)(*[int(v) for f in feats_t4_c2f for v in f.shape[1:3]])
     fp = _ptr_array(feats_t4_c2f)
     agg = np.ascontiguousarray(agg, dtype=np.float32)
-    rc = _lib.lib().surf_costvol(_p(parents), _p(idx), n, int(D), fp, hw, int(stage), cams.nv, _np_ptr(cams.intrs),
-                                 _np_ptr(cams.w2c), _np_ptr(agg), _p(coords), _p(feat), _p(keep), _stream())
-    _lib.check(rc, "surf_costvol")
+    _lib.lib().surf_costvol(_p(parents), _p(idx), n, int(D), fp, hw, int(stage), cams.nv, _np_ptr(cams.intrs),
+                            _np_ptr(cams.w2c), _np_ptr(agg), _p(coords), _p(feat), _p(keep), _stream())
     return coords, feat, keep
 
 
@@ -1148,7 +1123,7 @@ def compact(flags):
     ws = torch.empty(_lib.lib().surf_compact_workspace_ints(n), dtype=torch.int32, device=dev)
     idx = torch.empty(n, dtype=torch.int32, device=dev)
     total = torch.empty(1, dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().surf_compact(_p(flags), n, _p(ws), _p(idx), _p(total), _stream()), "surf_compact")
+    _lib.lib().surf_compact(_p(flags), n, _p(ws), _p(idx), _p(total), _stream())
     return idx[:int(total.item())]
 
 
@@ -1162,7 +1137,7 @@ def compact_counted(flags):
     ws = torch.empty(_lib.lib().surf_compact_workspace_ints(n), dtype=torch.int32, device=dev)
     idx = torch.empty(n, dtype=torch.int32, device=dev)
     total = torch.empty(1, dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().surf_compact(_p(flags), n, _p(ws), _p(idx), _p(total), _stream()), "surf_compact")
+    _lib.lib().surf_compact(_p(flags), n, _p(ws), _p(idx), _p(total), _stream())
     return idx, total
 
 
@@ -1174,14 +1149,13 @@ def gather_rows(src, idx, shift=0, dst=None, dst_off=0):
     n = idx.shape[0]
     if dst is None:
         dst = torch.empty(n, w, dtype=src.dtype, device=src.device)
-    rc = _lib.lib().surf_gather_rows(_p(src), _p(idx), n, w, int(shift), dst.shape[1], int(dst_off), _p(dst), _stream())
-    _lib.check(rc, "surf_gather_rows")
+    _lib.lib().surf_gather_rows(_p(src), _p(idx), n, w, int(shift), dst.shape[1], int(dst_off), _p(dst), _stream())
     return dst
 
 
 def compose_index(a, b):
     out = torch.empty_like(b)
-    _lib.check(_lib.lib().surf_compose_index(_p(a), _p(b), b.shape[0], _p(out), _stream()), "surf_compose_index")
+    _lib.lib().surf_compose_index(_p(a), _p(b), b.shape[0], _p(out), _stream())
     return out
 
 
@@ -1192,9 +1166,7 @@ def densify(coords, rows, D, prev=None):
     dev = coords.device
     dense = torch.empty(D, D, D, dtype=torch.float32, device=dev)
     table = torch.empty(D, D, D, dtype=torch.int32, device=dev)
-    rc = _lib.lib().surf_densify(_p(coords), _p(rows), rows.shape[1], coords.shape[0], int(D), _p(prev), _p(dense), _p(table),
-                                 _stream())
-    _lib.check(rc, "surf_densify")
+    _lib.lib().surf_densify(_p(coords), _p(rows), rows.shape[1], coords.shape[0], int(D), _p(prev), _p(dense), _p(table), _stream())
     return dense, table
 
 
@@ -1216,13 +1188,12 @@ def matching_depth(mvol, cams, near_fars, H, W, res_level, n, pre_depths=None, r
         _chk(jitter, torch.float32, "jitter")
         assert tuple(jitter.shape) == (cams.nv, h * w, 2)
     stats = torch.empty(cams.nv, h, w, 4, dtype=torch.float32, device=dev) if saved is not None else None
-    rc = _lib.lib().surf_matching_depth(_p(mvol), int(mvol.shape[0]), cams.nv, _np_ptr(cams.kinv), _np_ptr(cams.c2w),
-                                        _np_ptr(cams.rinv), _np_ptr(nf), H, W, h, w, _p(lin_x), _p(lin_y), _p(lin_n), int(n),
-                                        _p(pre_depths), ctypes.c_float(float(ratio_cur)), ctypes.c_float(float(ratio_prev)),
-                                        _p(jitter), _p(lr), _p(full), _p(stats), _stream())
+    _lib.lib().surf_matching_depth(_p(mvol), int(mvol.shape[0]), cams.nv, _np_ptr(cams.kinv), _np_ptr(cams.c2w),
+                                   _np_ptr(cams.rinv), _np_ptr(nf), H, W, h, w, _p(lin_x), _p(lin_y), _p(lin_n), int(n),
+                                   _p(pre_depths), float(ratio_cur), float(ratio_prev),
+                                   _p(jitter), _p(lr), _p(full), _p(stats), _stream())
     if saved is not None:
         saved["stats"] = stats
-    _lib.check(rc, "surf_matching_depth")
     return (full, lr) if return_lr else full
 
 
@@ -1249,12 +1220,11 @@ def matching_depth_backward(mvol, cams, near_fars, H, W, res_level, n, g_full, p
         dmvol = torch.zeros_like(mvol)
     n_views = len(set(int(v) for v in views))
     with _timed("matching_depth_bwd", n_views * h * w * int(n) * (1 if pre_depths is None else 2)):
-        rc = _lib.lib().surf_matching_depth_backward(_p(mvol), int(mvol.shape[0]), cams.nv, _np_ptr(cams.kinv), _np_ptr(cams.c2w),
-                                                     _np_ptr(cams.rinv), _np_ptr(nf), H, W, h, w, _p(lin_x), _p(lin_y), _p(lin_n),
-                                                     int(n), _p(pre_depths), ctypes.c_float(float(ratio_cur)),
-                                                     ctypes.c_float(float(ratio_prev)), _p(jitter), _p(g_full), int(views[0]), int(views[1]),
-                                                     _p(g_lr), _p(dmvol), _p(stats), _stream())
-    _lib.check(rc, "surf_matching_depth_backward")
+        _lib.lib().surf_matching_depth_backward(_p(mvol), int(mvol.shape[0]), cams.nv, _np_ptr(cams.kinv), _np_ptr(cams.c2w),
+                                                _np_ptr(cams.rinv), _np_ptr(nf), H, W, h, w, _p(lin_x), _p(lin_y), _p(lin_n),
+                                                int(n), _p(pre_depths), float(ratio_cur),
+                                                float(ratio_prev), _p(jitter), _p(g_full), int(views[0]), int(views[1]),
+                                                _p(g_lr), _p(dmvol), _p(stats), _stream())
     return dmvol
 
 
@@ -1264,9 +1234,8 @@ def densify_backward(coords, table, g_dense, g_rows, g_prev=None):
     _chk(g_dense, torch.float32, "g_dense")
     _chk(g_rows, torch.float32, "g_rows")
     D = int(g_dense.shape[0])
-    rc = _lib.lib().surf_densify_backward(_p(coords), coords.shape[0], D, _p(table), _p(g_dense), g_rows.shape[1], _p(g_rows),
-                                          _p(g_prev), _stream())
-    _lib.check(rc, "surf_densify_backward")
+    _lib.lib().surf_densify_backward(_p(coords), coords.shape[0], D, _p(table), _p(g_dense), g_rows.shape[1], _p(g_rows),
+                                     _p(g_prev), _stream())
     return g_rows, g_prev
 
 
@@ -1275,9 +1244,8 @@ def scatter_rows_add(g_dst, idx, g_src, shift=0, dst_off=0):
     _chk(g_dst, torch.float32, "g_dst")
     _chk(g_src, torch.float32, "g_src")
     _chk(idx, torch.int32, "idx")
-    rc = _lib.lib().surf_scatter_rows_add(_p(g_dst), _p(idx), idx.shape[0], g_src.shape[1], int(shift), g_dst.shape[1],
-                                          int(dst_off), _p(g_src), _stream())
-    _lib.check(rc, "surf_scatter_rows_add")
+    _lib.lib().surf_scatter_rows_add(_p(g_dst), _p(idx), idx.shape[0], g_src.shape[1], int(shift), g_dst.shape[1],
+                                     int(dst_off), _p(g_src), _stream())
     return g_src
 
 
@@ -1293,10 +1261,9 @@ def costvol_backward(feats_t4_c2f, gfeats_t4_c2f, stage, D, cams, agg, coords, g
     ws = torch.empty(_lib.lib().surf_costvol_backward_workspace_floats_for(coords.shape[0], cams.nv, hw),
                      dtype=torch.float32, device=g.device)
     with _timed("costvol_bwd", int(coords.shape[0]) * cams.nv * (4 - int(stage))):
-        rc = _lib.lib().surf_costvol_backward(_p(coords), _p(g), coords.shape[0], int(D), _ptr_array(feats_t4_c2f),
-                                              _ptr_array(gfeats_t4_c2f), hw, int(stage), cams.nv, _np_ptr(cams.intrs),
-                                              _np_ptr(cams.w2c), _np_ptr(agg), _p(ws), _p(g_agg), _stream())
-    _lib.check(rc, "surf_costvol_backward")
+        _lib.lib().surf_costvol_backward(_p(coords), _p(g), coords.shape[0], int(D), _ptr_array(feats_t4_c2f),
+                                         _ptr_array(gfeats_t4_c2f), hw, int(stage), cams.nv, _np_ptr(cams.intrs),
+                                         _np_ptr(cams.w2c), _np_ptr(agg), _p(ws), _p(g_agg), _stream())
 
 
 def raster_first_hit(vertices, faces, intr, c2w, hw, upscale=1):
@@ -1309,9 +1276,8 @@ def raster_first_hit(vertices, faces, intr, c2w, hw, upscale=1):
     K = np.ascontiguousarray(intr.detach().to("cpu", torch.float32)[:3, :3].contiguous().numpy())
     w2c = np.ascontiguousarray(torch.inverse(c2w.detach().to("cpu", torch.float32))[:3, :4].contiguous().numpy())
     zbuf = torch.full((Hup, Wup), -1, dtype=torch.int64, device=vertices.device)      # all ones = empty
-    rc = _lib.lib().surf_raster_first_hit(_p(vertices), _p(faces), faces.shape[0], _np_ptr(K), _np_ptr(w2c), h, w, Hup, Wup,
-                                          _p(zbuf), _stream())
-    _lib.check(rc, "surf_raster_first_hit")
+    _lib.lib().surf_raster_first_hit(_p(vertices), _p(faces), faces.shape[0], _np_ptr(K), _np_ptr(w2c), h, w, Hup, Wup,
+                                     _p(zbuf), _stream())
     return torch.where(zbuf == -1, torch.full_like(zbuf, -1), zbuf & 0xffffffff)
 
 
@@ -1343,14 +1309,13 @@ def mesh_sample_points(vertices, triangles, thresh):
         raise IndexError(f"triangles index vertices {lo}..{hi} of {nv}")
     L = _lib.lib()
     counts = torch.empty(nt, dtype=torch.int64, device=vertices.device)
-    _lib.check(L.surf_dtu_sample_count(_p(vertices), _p(triangles), nt, float(thresh), _p(counts), _stream()), "surf_dtu_sample_count")
+    L.surf_dtu_sample_count(_p(vertices), _p(triangles), nt, float(thresh), _p(counts), _stream())
     ends = torch.cumsum(counts, 0)
     total = int(ends[-1])
     out = torch.empty(nv + total, 3, dtype=torch.float64, device=vertices.device)
     out[:nv] = vertices
     if total:
-        _lib.check(L.surf_dtu_sample_write(_p(vertices), _p(triangles), nt, float(thresh), _p(ends - counts), _p(out[nv:]), _stream()),
-                   "surf_dtu_sample_write")
+        L.surf_dtu_sample_write(_p(vertices), _p(triangles), nt, float(thresh), _p(ends - counts), _p(out[nv:]), _stream())
     return out
 
 
@@ -1374,7 +1339,7 @@ def thin_points(points, thresh, max_rounds=10000):
         cell = 1.0
     A = THIN_AXIS_CELLS
     keys = torch.empty(n, dtype=torch.int64, device=dev)
-    _lib.check(L.surf_dtu_cell_keys(_p(points), n, lo[0], lo[1], lo[2], cell, A, A, A, _p(keys), _stream()), "surf_dtu_cell_keys")
+    L.surf_dtu_cell_keys(_p(points), n, lo[0], lo[1], lo[2], cell, A, A, A, _p(keys), _stream())
     skeys, order = torch.sort(keys, stable=True)              # stable: a cell lists its points in shuffled order
     ucell, scell, counts = torch.unique_consecutive(skeys, return_inverse=True, return_counts=True)
     cstart = torch.zeros(ucell.shape[0] + 1, dtype=torch.int32, device=dev)
@@ -1386,8 +1351,8 @@ def thin_points(points, thresh, max_rounds=10000):
     undecided = torch.empty(1, dtype=torch.int32, device=dev)
     rounds = 0
     while True:
-        _lib.check(L.surf_dtu_thin_round(_p(spts), _p(sidx), _p(scell), _p(ucell), _p(cstart), n, ucell.shape[0], float(thresh),
-                                         _p(state), _p(undecided), _stream()), "surf_dtu_thin_round")
+        L.surf_dtu_thin_round(_p(spts), _p(sidx), _p(scell), _p(ucell), _p(cstart), n, ucell.shape[0], float(thresh),
+                              _p(state), _p(undecided), _stream())
         rounds += 1
         if int(undecided.item()) == 0:
             break
@@ -1420,15 +1385,14 @@ def nearest_dist_capped(queries, ref, max_dist):
             break
         cell *= 1.25
     keys = torch.empty(r, dtype=torch.int64, device=dev)
-    _lib.check(L.surf_dtu_cell_keys(_p(ref), r, lo[0], lo[1], lo[2], cell, dims[0], dims[1], dims[2], _p(keys), _stream()),
-               "surf_dtu_cell_keys")
+    L.surf_dtu_cell_keys(_p(ref), r, lo[0], lo[1], lo[2], cell, dims[0], dims[1], dims[2], _p(keys), _stream())
     skeys, order = torch.sort(keys)
     cstart = torch.zeros(dims[0] * dims[1] * dims[2] + 1, dtype=torch.int32, device=dev)
     cstart[1:] = torch.cumsum(torch.bincount(skeys, minlength=dims[0] * dims[1] * dims[2]), 0)
     sref = ref[order].contiguous()
     out = torch.empty(m, dtype=torch.float64, device=dev)
-    _lib.check(L.surf_dtu_nearest(_p(queries), m, _p(sref), _p(cstart), lo[0], lo[1], lo[2], cell, dims[0], dims[1], dims[2],
-                                  float(max_dist), _p(out), _stream()), "surf_dtu_nearest")
+    L.surf_dtu_nearest(_p(queries), m, _p(sref), _p(cstart), lo[0], lo[1], lo[2], cell, dims[0], dims[1], dims[2],
+                       float(max_dist), _p(out), _stream())
     return out
 
 
@@ -1454,7 +1418,7 @@ def clean_dilate(masks, radius):
     out = torch.empty_like(m)
     if m.numel():
         nv, h, w = m.shape
-        _lib.check(_lib.lib().surf_clean_dilate(_p(m), nv, h, w, int(radius), _p(out), _stream()), "surf_clean_dilate")
+        _lib.lib().surf_clean_dilate(_p(m), nv, h, w, int(radius), _p(out), _stream())
     return out.view(torch.bool)
 
 
@@ -1470,8 +1434,7 @@ def clean_hull_count(vertices, masks, intrs, c2ws):
     if n == 0 or nv == 0:
         return n_seen
     cams = _camera_rows(intrs, c2ws, vertices.device)
-    _lib.check(_lib.lib().surf_clean_hull_count(_p(vertices), n, _p(m), _p(cams), nv, h, w, _p(n_seen), _stream()),
-               "surf_clean_hull_count")
+    _lib.lib().surf_clean_hull_count(_p(vertices), n, _p(m), _p(cams), nv, h, w, _p(n_seen), _stream())
     return n_seen
 
 
@@ -1481,8 +1444,7 @@ def clean_face_keep(n_seen, faces, min_nb_visible):
     _chk(faces, torch.int32, "faces")
     keep = torch.empty(faces.shape[0], dtype=torch.uint8, device=faces.device)
     if faces.shape[0]:
-        _lib.check(_lib.lib().surf_clean_face_keep(_p(n_seen), _p(faces), faces.shape[0], int(min_nb_visible), _p(keep), _stream()),
-                   "surf_clean_face_keep")
+        _lib.lib().surf_clean_face_keep(_p(n_seen), _p(faces), faces.shape[0], int(min_nb_visible), _p(keep), _stream())
     return keep.view(torch.bool)
 
 
@@ -1508,10 +1470,8 @@ def clean_visible_faces(vertices, faces, masks, intrs, c2ws, upscale):
         K = np.ascontiguousarray(intrs[i].detach().to("cpu", torch.float32)[:3, :3].contiguous().numpy())
         w2c = np.ascontiguousarray(torch.inverse(c2ws[i].detach().to("cpu", torch.float32))[:3, :4].contiguous().numpy())
         zbuf.fill_(-1)
-        _lib.check(L.surf_raster_first_hit(_p(vertices), _p(faces), nf, _np_ptr(K), _np_ptr(w2c), h, w, Hup, Wup, _p(zbuf),
-                                           _stream()), "surf_raster_first_hit")
-        _lib.check(L.surf_clean_mark_visible(_p(zbuf), Hup, Wup, _p(m[i]), h, w, upscale, nf, _p(seen), _stream()),
-                   "surf_clean_mark_visible")
+        L.surf_raster_first_hit(_p(vertices), _p(faces), nf, _np_ptr(K), _np_ptr(w2c), h, w, Hup, Wup, _p(zbuf), _stream())
+        L.surf_clean_mark_visible(_p(zbuf), Hup, Wup, _p(m[i]), h, w, upscale, nf, _p(seen), _stream())
     return seen.view(torch.bool)
 
 
@@ -1526,7 +1486,7 @@ def clean_components(faces, min_len, return_labels=False):
         return (e, torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.int32, device=dev)) if return_labels else e
     L = _lib.lib()
     slots = L.surf_clean_components_slots(nf)
-    if slots < 0:
+    if slots < 0:       # an int64_t size query reports its SURF_E_* through the value: no errcheck is bound, so checked here
         _lib.check(int(slots), "surf_clean_components_slots")
     try:
         keys = torch.empty(slots, dtype=torch.int64, device=dev)
@@ -1537,10 +1497,10 @@ def clean_components(faces, min_len, return_labels=False):
         size = torch.empty(nf, dtype=torch.int32, device=dev)
         has_nb = torch.empty(nf, dtype=torch.uint8, device=dev)
         keep = torch.empty(nf, dtype=torch.uint8, device=dev)
-    except torch.cuda.OutOfMemoryError:
+    except torch.cuda.OutOfMemoryError:     # no entry point was called: the limit error is raised in the library's words
         _lib.check(-2, f"surf_clean_components: the edge table of {nf} faces does not fit the device")
-    _lib.check(L.surf_clean_components(_p(faces), nf, int(min(max(int(min_len), -1), 1 << 62)), _p(keys), _p(owner), _p(shared), slots,
-                                       _p(edge_slot), _p(parent), _p(has_nb), _p(size), _p(keep), _stream()), "surf_clean_components")
+    L.surf_clean_components(_p(faces), nf, int(min(max(int(min_len), -1), 1 << 62)), _p(keys), _p(owner), _p(shared), slots,
+                            _p(edge_slot), _p(parent), _p(has_nb), _p(size), _p(keep), _stream())
     keep = keep.view(torch.bool)
     return (keep, parent, size) if return_labels else keep
 
@@ -1561,7 +1521,7 @@ def clean_update_faces(vertices, faces, keep, compact_vertices=True):
     fscan = torch.cumsum(k, 0, dtype=torch.int64)
     if compact_vertices:
         used = torch.zeros(nv, dtype=torch.uint8, device=dev)
-        _lib.check(L.surf_clean_mark_used(_p(faces), _p(k), nf, nv, _p(used), _stream()), "surf_clean_mark_used")
+        L.surf_clean_mark_used(_p(faces), _p(k), nf, nv, _p(used), _stream())
         vscan = torch.cumsum(used, 0, dtype=torch.int64)
         n_f, n_v = (int(v) for v in torch.stack([fscan[-1], vscan[-1]]).tolist())
     else:
@@ -1569,14 +1529,12 @@ def clean_update_faces(vertices, faces, keep, compact_vertices=True):
         n_f, n_v = int(fscan[-1].item()), nv
     out_f = torch.empty(n_f, 3, dtype=torch.int32, device=dev)
     if n_f:
-        _lib.check(L.surf_clean_compact_faces(_p(faces), _p(k), _p(fscan), _p(vscan), nf, nv, _p(out_f), _stream()),
-                   "surf_clean_compact_faces")
+        L.surf_clean_compact_faces(_p(faces), _p(k), _p(fscan), _p(vscan), nf, nv, _p(out_f), _stream())
     if not compact_vertices:
         return vertices, out_f
     out_v = torch.empty(n_v, 3, dtype=vertices.dtype, device=dev)
     if n_v:
-        _lib.check(L.surf_clean_compact_rows(_p(vertices), vertices.element_size(), _p(used), _p(vscan), nv, _p(out_v), _stream()),
-                   "surf_clean_compact_rows")
+        L.surf_clean_compact_rows(_p(vertices), vertices.element_size(), _p(used), _p(vscan), nv, _p(out_v), _stream())
     return out_v, out_f
 
 
@@ -1597,8 +1555,7 @@ def dtu_clean_dilate(masks, half_widths):
     if masks.numel():
         nv, h, w = masks.shape
         hw = torch.tensor(half, dtype=torch.int32).to(masks.device)
-        _lib.check(_lib.lib().surf_dtu_clean_dilate(_p(masks), nv, h, w, _p(hw), len(half), _p(out), _stream()),
-                   "surf_dtu_clean_dilate")
+        _lib.lib().surf_dtu_clean_dilate(_p(masks), nv, h, w, _p(hw), len(half), _p(out), _stream())
     return out
 
 
@@ -1617,8 +1574,7 @@ def dtu_clean_points_in_masks(vertices, dilated, proj):
     if P.dtype != torch.float32 or P.shape[0] != nv or tuple(P.shape[1:]) not in ((4, 4), (3, 4)):
         raise TypeError("proj: expected (n_views, 4, 4) or (n_views, 3, 4) float32")
     P = P[:, :3, :].contiguous().to(vertices.device)
-    _lib.check(_lib.lib().surf_dtu_clean_points_in_masks(_p(vertices), n, _p(dilated), _p(P), nv, h, w, _p(count), _stream()),
-               "surf_dtu_clean_points_in_masks")
+    _lib.lib().surf_dtu_clean_points_in_masks(_p(vertices), n, _p(dilated), _p(P), nv, h, w, _p(count), _stream())
     return count
 
 
@@ -1638,19 +1594,17 @@ def dtu_clean_remove_vertices(vertices, faces, count, minimal_vis):
     L = _lib.lib()
     vkeep = torch.empty(nv, dtype=torch.uint8, device=dev)
     fkeep = torch.empty(nf, dtype=torch.uint8, device=dev)
-    _lib.check(L.surf_dtu_clean_keep(_p(count), nv, _p(faces) if nf else None, nf, int(minimal_vis), _p(vkeep),
-                                     _p(fkeep) if nf else None, _stream()), "surf_dtu_clean_keep")
+    L.surf_dtu_clean_keep(_p(count), nv, _p(faces) if nf else None, nf, int(minimal_vis), _p(vkeep),
+                          _p(fkeep) if nf else None, _stream())
     vscan = torch.cumsum(vkeep, 0, dtype=torch.int64)
     fscan = torch.cumsum(fkeep, 0, dtype=torch.int64)
     n_v, n_f = (int(x) for x in torch.stack([vscan[-1], fscan[-1] if nf else torch.zeros_like(vscan[-1])]).tolist())
     out_v = torch.empty(n_v, 3, dtype=vertices.dtype, device=dev)
     out_f = torch.empty(n_f, 3, dtype=torch.int32, device=dev)
     if n_v:
-        _lib.check(L.surf_clean_compact_rows(_p(vertices), vertices.element_size(), _p(vkeep), _p(vscan), nv, _p(out_v), _stream()),
-                   "surf_clean_compact_rows")
+        L.surf_clean_compact_rows(_p(vertices), vertices.element_size(), _p(vkeep), _p(vscan), nv, _p(out_v), _stream())
     if n_f:
-        _lib.check(L.surf_clean_compact_faces(_p(faces), _p(fkeep), _p(fscan), _p(vscan), nf, nv, _p(out_f), _stream()),
-                   "surf_clean_compact_faces")
+        L.surf_clean_compact_faces(_p(faces), _p(fkeep), _p(fscan), _p(vscan), nf, nv, _p(out_f), _stream())
     return out_v, out_f, vkeep.view(torch.bool)
 
 
@@ -1683,9 +1637,8 @@ def finetune_rays(px, py, kinv, c2w, image, depth=None):
     color = torch.empty(n, 3, dtype=torch.float32, device=dev)
     pseudo = torch.empty(n, dtype=torch.float32, device=dev) if depth is not None else None
     if n:
-        _lib.check(_lib.lib().surf_finetune_rays(_p(px), _p(py), int(px.dtype == torch.int32), n, _p(kinv), _p(c2w), _p(image),
-                                                 _p(depth), h, w, _p(rays_o), _p(rays_d), _p(color), _p(pseudo), _stream()),
-                   "surf_finetune_rays")
+        _lib.lib().surf_finetune_rays(_p(px), _p(py), int(px.dtype == torch.int32), n, _p(kinv), _p(c2w), _p(image),
+                                      _p(depth), h, w, _p(rays_o), _p(rays_d), _p(color), _p(pseudo), _stream())
     return rays_o, rays_d, color, pseudo
 
 
@@ -1697,8 +1650,7 @@ def finetune_gather_pts(pts, idx):
         raise ValueError("finetune_gather_pts: pts (N, 3), idx (M,)")
     out = torch.empty(idx.shape[0], 3, dtype=torch.float32, device=pts.device)
     if idx.shape[0]:
-        _lib.check(_lib.lib().surf_finetune_gather_pts(_p(pts), pts.shape[0], _p(idx), idx.shape[0], _p(out), _stream()),
-                   "surf_finetune_gather_pts")
+        _lib.lib().surf_finetune_gather_pts(_p(pts), pts.shape[0], _p(idx), idx.shape[0], _p(out), _stream())
     return out
 
 
@@ -1719,8 +1671,7 @@ def vertex_points(vertices):
     pts = torch.empty(n, 3, dtype=torch.float32, device=dev)
     idx = torch.empty(n, dtype=torch.int32, device=dev)
     if n:
-        _lib.check(_lib.lib().surf_vertex_points(_p(vertices), int(vertices.dtype == torch.float64), n, _p(pts), _p(idx), _stream()),
-                   "surf_vertex_points")
+        _lib.lib().surf_vertex_points(_p(vertices), int(vertices.dtype == torch.float64), n, _p(pts), _p(idx), _stream())
     return pts, idx
 
 
@@ -1739,8 +1690,7 @@ def vertex_finish(grad, color, n_valid, normals=None, colors=None):
     if tuple(normals.shape) != (n, 3) or tuple(colors.shape) != (n, 3):
         raise ValueError("vertex_finish: normals (V, 3), colors (V, 3)")
     if n:
-        _lib.check(_lib.lib().surf_vertex_finish(_p(grad), _p(color), _p(n_valid), n, _p(normals), _p(colors), _stream()),
-                   "surf_vertex_finish")
+        _lib.lib().surf_vertex_finish(_p(grad), _p(color), _p(n_valid), n, _p(normals), _p(colors), _stream())
     return normals, colors
 
 
@@ -1765,20 +1715,19 @@ def marching_cubes(u, isovalue=0.0):
     L = _lib.lib()
     flags = torch.empty(nx * ny * nz, dtype=torch.uint8, device=dev)
     iso = ctypes.c_double(float(isovalue))       # PyMCubes takes the isovalue as a double
-    _lib.check(L.surf_mc_classify(_p(u), nx, ny, nz, iso, _p(flags), _stream()), "surf_mc_classify")
+    L.surf_mc_classify(_p(u), nx, ny, nz, iso, _p(flags), _stream())
     active = compact(flags)
     m = int(active.shape[0])
     if m == 0:
         return torch.zeros(0, 3, dtype=torch.float64, device=dev), torch.zeros(0, 3, dtype=torch.int32, device=dev)
     ws = torch.empty(L.surf_mc_workspace_ints(m), dtype=torch.int32, device=dev)
     totals = torch.empty(2, dtype=torch.int32, device=dev)
-    _lib.check(L.surf_mc_count(_p(flags), _p(active), m, _p(ws), _p(totals), _stream()), "surf_mc_count")
+    L.surf_mc_count(_p(flags), _p(active), m, _p(ws), _p(totals), _stream())
     n_v, n_t = (int(v) for v in totals.tolist())
     vertices = torch.empty(n_v, 3, dtype=torch.float64, device=dev)
     triangles = torch.empty(n_t, 3, dtype=torch.int32, device=dev)
     vbase = torch.empty(nx * ny * nz, dtype=torch.int32, device=dev)
-    _lib.check(L.surf_mc_emit(_p(u), nx, ny, nz, iso, _p(flags), _p(active), m, _p(ws), _p(vbase), _p(vertices), _p(triangles),
-                              _stream()), "surf_mc_emit")
+    L.surf_mc_emit(_p(u), nx, ny, nz, iso, _p(flags), _p(active), m, _p(ws), _p(vbase), _p(vertices), _p(triangles), _stream())
     return vertices, triangles
 
 
@@ -1819,9 +1768,8 @@ def sdf_bricks(axes, volumes, packed, bricks, resolution, out, sign=-1.0):
     fn = getattr(_lib.lib(), name)
     for j0 in range(0, m, BAND_SPLIT_BRICKS):
         k = min(BAND_SPLIT_BRICKS, m - j0)
-        rc = fn(_p(axes[0]), _p(axes[1]), _p(axes[2]), int(resolution), _p(bricks[j0:]), k, volumes._vp, volumes._tp, volumes._dp,
-                volumes.n, _p(packed), _p(out[j0 * 512:]), ctypes.c_float(sign), _stream())
-        _lib.check(rc, name)
+        fn(_p(axes[0]), _p(axes[1]), _p(axes[2]), int(resolution), _p(bricks[j0:]), k, volumes._vp, volumes._tp, volumes._dp,
+           volumes.n, _p(packed), _p(out[j0 * 512:]), float(sign), _stream())
 
 
 def band_points(axes, bricks, resolution):
@@ -1832,8 +1780,7 @@ def band_points(axes, bricks, resolution):
     _chk(bricks, torch.int32, "bricks")
     m = int(bricks.shape[0])
     pts = torch.empty(m * 512, 3, dtype=torch.float32, device=bricks.device)
-    _lib.check(_lib.lib().surf_band_points(_p(axes[0]), _p(axes[1]), _p(axes[2]), _p(bricks), m, int(resolution), _p(pts), _stream()),
-               "surf_band_points")
+    _lib.lib().surf_band_points(_p(axes[0]), _p(axes[1]), _p(axes[2]), _p(bricks), m, int(resolution), _p(pts), _stream())
     return pts
 
 
@@ -1845,8 +1792,8 @@ def band_screen(uc, caxes, resolution, isovalue, margin):
         _chk(ax, torch.float32, "coarse axis")
     L = _lib.lib()
     mark = torch.zeros(int(L.surf_band_table_size(int(resolution))), dtype=torch.uint8, device=uc.device)
-    _lib.check(L.surf_band_screen(_p(uc), _p(caxes[0]), _p(caxes[1]), _p(caxes[2]), int(resolution), ctypes.c_double(float(isovalue)),
-                                  ctypes.c_double(float(margin)), _p(mark), _stream()), "surf_band_screen")
+    L.surf_band_screen(_p(uc), _p(caxes[0]), _p(caxes[1]), _p(caxes[2]), int(resolution), ctypes.c_double(float(isovalue)),
+                       ctypes.c_double(float(margin)), _p(mark), _stream())
     return mark
 
 
@@ -1888,9 +1835,9 @@ def band_grow(resolution, isovalue, mark, evaluate):
     n_slots, passes, seeded, grown = 0, 0, 0, 0
     for _ in range(nt + 1):                       # every pass but the last adds a cell brick
         st = _stream()
-        _lib.check(L.surf_band_promote(_p(mark), _p(is_cell), _p(table), _p(need), n, st), "surf_band_promote")
-        _lib.check(L.surf_compact(_p(mark), nt, _p(ws), _p(new_cell), _p(counts), st), "surf_compact")
-        _lib.check(L.surf_compact(_p(need), nt, _p(ws), _p(new_eval), _p(counts[1:]), st), "surf_compact")
+        L.surf_band_promote(_p(mark), _p(is_cell), _p(table), _p(need), n, st)
+        L.surf_compact(_p(mark), nt, _p(ws), _p(new_cell), _p(counts), st)
+        L.surf_compact(_p(need), nt, _p(ws), _p(new_eval), _p(counts[1:]), st)
         n_cell, n_eval = (int(v) for v in counts.tolist())            # the pass's one host read
         if n_cell == 0:
             break
@@ -1901,13 +1848,13 @@ def band_grow(resolution, isovalue, mark, evaluate):
             b2[:n_slots] = bricks[:n_slots]
             v2[:n_slots * 512] = values[:n_slots * 512]
             bricks, values = b2, v2
-        _lib.check(L.surf_band_assign(_p(new_eval), n_eval, n_slots, _p(table), _p(bricks), _p(need), st), "surf_band_assign")
+        L.surf_band_assign(_p(new_eval), n_eval, n_slots, _p(table), _p(bricks), _p(need), st)
         if n_eval:
             evaluate(bricks[n_slots:n_slots + n_eval], values[n_slots * 512:(n_slots + n_eval) * 512])
         n_slots += n_eval
         st = _stream()
-        _lib.check(L.surf_band_clear(_p(new_cell), n_cell, _p(mark), st), "surf_band_clear")
-        _lib.check(L.surf_band_grow(_p(values), _p(table), _p(is_cell), _p(new_cell), n_cell, n, iso, _p(mark), st), "surf_band_grow")
+        L.surf_band_clear(_p(new_cell), n_cell, _p(mark), st)
+        L.surf_band_grow(_p(values), _p(table), _p(is_cell), _p(new_cell), n_cell, n, iso, _p(mark), st)
         if passes == 0:
             seeded = n_cell
         else:
@@ -1931,25 +1878,24 @@ def marching_cubes_band(band, isovalue=0.0):
     if ns == 0:
         return empty
     flags = torch.empty(ns * 512, dtype=torch.uint8, device=dev)
-    _lib.check(L.surf_band_classify(_p(band.values), _p(band.table), _p(band.is_cell), _p(band.bricks), ns, n, iso, _p(flags), _stream()),
-               "surf_band_classify")
+    L.surf_band_classify(_p(band.values), _p(band.table), _p(band.is_cell), _p(band.bricks), ns, n, iso, _p(flags), _stream())
     pos = compact(flags)
     m = int(pos.shape[0])
     if m == 0:
         return empty
     keys = torch.empty(m, dtype=torch.int64, device=dev)
-    _lib.check(L.surf_band_keys(_p(pos), m, _p(band.bricks), n, _p(keys), _stream()), "surf_band_keys")
+    L.surf_band_keys(_p(pos), m, _p(band.bricks), n, _p(keys), _stream())
     keys = torch.sort(keys).values                       # dense order: ascending lattice keys
-    _lib.check(L.surf_band_rank(_p(keys), m, _p(band.table), n, _p(pos), _stream()), "surf_band_rank")
+    L.surf_band_rank(_p(keys), m, _p(band.table), n, _p(pos), _stream())
     ws = torch.empty(L.surf_mc_workspace_ints(m), dtype=torch.int32, device=dev)
     totals = torch.empty(2, dtype=torch.int32, device=dev)
-    _lib.check(L.surf_mc_count(_p(flags), _p(pos), m, _p(ws), _p(totals), _stream()), "surf_mc_count")
+    L.surf_mc_count(_p(flags), _p(pos), m, _p(ws), _p(totals), _stream())
     n_v, n_t = (int(v) for v in totals.tolist())
     vertices = torch.empty(n_v, 3, dtype=torch.float64, device=dev)
     triangles = torch.empty(n_t, 3, dtype=torch.int32, device=dev)
     vbase = torch.empty(ns * 512, dtype=torch.int32, device=dev)
-    _lib.check(L.surf_band_emit(_p(band.values), _p(band.table), n, iso, _p(flags), _p(keys), _p(pos), m, _p(ws), _p(vbase), _p(vertices),
-                                _p(triangles), _stream()), "surf_band_emit")
+    L.surf_band_emit(_p(band.values), _p(band.table), n, iso, _p(flags), _p(keys), _p(pos), m, _p(ws), _p(vbase), _p(vertices),
+                     _p(triangles), _stream())
     return vertices, triangles
 
 
@@ -1962,8 +1908,7 @@ SUBM, DOWN, UP = 0, 1, 2
 
 def table_from_coords(coords, D):
     table = torch.full((D, D, D), -1, dtype=torch.int32, device=coords.device)
-    _lib.check(_lib.lib().surf_table_from_coords(_p(coords), coords.shape[0], int(D), _p(table), _stream()),
-               "surf_table_from_coords")
+    _lib.lib().surf_table_from_coords(_p(coords), coords.shape[0], int(D), _p(table), _stream())
     return table
 
 
@@ -1996,16 +1941,15 @@ def down_sites(coords, D, rule=DEFAULT_DOWN_RULE, q_max=None):
         bbox = _pad0_ranges[key]
     else:
         bbox = torch.empty(6, dtype=torch.int32, device=dev)          # stays on the device: no host round trip
-        _lib.check(_lib.lib().surf_coords_bbox(_p(coords), coords.shape[0], _p(bbox), _stream()), "surf_coords_bbox")
+        _lib.lib().surf_coords_bbox(_p(coords), coords.shape[0], _p(bbox), _stream())
     marks = torch.zeros(D2 * D2 * D2, dtype=torch.uint8, device=dev)
-    _lib.check(_lib.lib().surf_mark_down_sites(_p(coords), coords.shape[0], int(D), _p(bbox), _p(marks), DOWN_RULES[rule],
-                                               _stream()), "surf_mark_down_sites")
+    _lib.lib().surf_mark_down_sites(_p(coords), coords.shape[0], int(D), _p(bbox), _p(marks), DOWN_RULES[rule], _stream())
     keys = compact(marks)
     c2 = torch.empty(keys.shape[0], 3, dtype=torch.int32, device=dev)
     t2 = torch.full((D2, D2, D2), -1, dtype=torch.int32, device=dev)
     if keys.shape[0] == 0:          # degenerate tiny lattices: no even site inside the inputs' bounding box
         return c2, t2, D2
-    _lib.check(_lib.lib().surf_sites_from_keys(_p(keys), keys.shape[0], D2, _p(c2), _p(t2), _stream()), "surf_sites_from_keys")
+    _lib.lib().surf_sites_from_keys(_p(keys), keys.shape[0], D2, _p(c2), _p(t2), _stream())
     return c2, t2, D2
 
 
@@ -2021,7 +1965,7 @@ def spconv_pack_weights(weight, thin=False):
     if nbytes == 0:
         return None
     packed = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
-    _lib.check(_lib.lib().surf_spconv_pack_weights(_p(weight), cin, cout, _p(packed), _stream()), "surf_spconv_pack_weights")
+    _lib.lib().surf_spconv_pack_weights(_p(weight), cin, cout, _p(packed), _stream())
     return packed
 
 
@@ -2043,23 +1987,20 @@ def spconv(x, in_table, out_coords, mode, weight, bn_scale=None, bn_shift=None, 
     if packed is not None:
         _chk(packed, torch.uint8, "packed weights")
         assert packed.numel() == _lib.lib().surf_spconv_packed_bytes(cin, cout)
-        rc = _lib.lib().surf_spconv_mfma(_p(x), cin, _p(in_table), int(in_table.shape[0]), _p(out_coords), out_coords.shape[0],
-                                         int(mode), _p(packed), cout, _p(bn_scale), _p(bn_shift), _p(skip), _p(out), int(bool(bf16)),
-                                         _stream())
-        _lib.check(rc, "surf_spconv_mfma")
+        _lib.lib().surf_spconv_mfma(_p(x), cin, _p(in_table), int(in_table.shape[0]), _p(out_coords), out_coords.shape[0],
+                                    int(mode), _p(packed), cout, _p(bn_scale), _p(bn_shift), _p(skip), _p(out), int(bool(bf16)),
+                                    _stream())
         return out
     if bf16 and bf16_rows and cin == 16 and cout == 8 and bn_scale is None and skip is None and (mode == SUBM or bf16_rows_all_modes):
         # the bf16 training policy: gather from the rows' bf16 shadow (attached by bn_train_relu / bn_relu_backward, or made here)
         r16 = getattr(x, "_rows16", None)
         if r16 is None:
             r16 = rows_to_bf16(x)
-        rc = _lib.lib().surf_spconv_rows16(_p(r16), cin, _p(in_table), int(in_table.shape[0]), _p(out_coords), out_coords.shape[0],
-                                           int(mode), _p(weight), cout, _p(out), _stream())
-        _lib.check(rc, "surf_spconv_rows16")
+        _lib.lib().surf_spconv_rows16(_p(r16), cin, _p(in_table), int(in_table.shape[0]), _p(out_coords), out_coords.shape[0],
+                                      int(mode), _p(weight), cout, _p(out), _stream())
         return out
-    rc = _lib.lib().surf_spconv(_p(x), cin, _p(in_table), int(in_table.shape[0]), _p(out_coords), out_coords.shape[0], int(mode),
-                                _p(weight), cout, _p(bn_scale), _p(bn_shift), _p(skip), _p(out), _stream())
-    _lib.check(rc, "surf_spconv")
+    _lib.lib().surf_spconv(_p(x), cin, _p(in_table), int(in_table.shape[0]), _p(out_coords), out_coords.shape[0], int(mode),
+                           _p(weight), cout, _p(bn_scale), _p(bn_shift), _p(skip), _p(out), _stream())
     return out
 
 
@@ -2136,12 +2077,11 @@ def spconv_backward(x, in_table, in_coords, out_table, out_coords, mode, weight,
         with _timed(f"spconv_wgrad<{cin},{cout}>", {"pairs": pairs, "sites": int(out_coords.shape[0])}):
             if use_mfma and _lib.lib().surf_spconv_wgrad_mfma_supported(wci, wco):
                 # round 5: the channel pairs for which the matrix-core form wins (spconv_wgrad_mfma.hip), fp32-equivalent
-                rc = _lib.lib().surf_spconv_wgrad_mfma(_p(wx), wci, _p(wtab), int(wtab.shape[0]), _p(wcoords), wcoords.shape[0],
-                                                       int(wmode), _p(wdy), wco, _p(dW), _stream())
-            else:
-                rc = _lib.lib().surf_spconv_wgrad(_p(wx), wci, _p(wtab), int(wtab.shape[0]), _p(wcoords), wcoords.shape[0],
+                _lib.lib().surf_spconv_wgrad_mfma(_p(wx), wci, _p(wtab), int(wtab.shape[0]), _p(wcoords), wcoords.shape[0],
                                                   int(wmode), _p(wdy), wco, _p(dW), _stream())
-        _lib.check(rc, "surf_spconv_wgrad")
+            else:
+                _lib.lib().surf_spconv_wgrad(_p(wx), wci, _p(wtab), int(wtab.shape[0]), _p(wcoords), wcoords.shape[0],
+                                             int(wmode), _p(wdy), wco, _p(dW), _stream())
 
     if on_side:     # a leaf of the sweep: on the side stream, forked BEFORE the input gradient is issued so that the two run
         with side.fork():       # side by side (the caller joins before it reads dW)
@@ -2174,10 +2114,9 @@ def bn_train_relu(x, bn, skip=None, saved=None, counters=None, shadow=False):
     ws = torch.empty(_lib.lib().surf_bn_workspace_bytes(C), dtype=torch.uint8, device=dev)
     momentum = 0.1 if bn.momentum is None else float(bn.momentum)
     track = bn.track_running_stats and bn.running_mean is not None
-    rc = _lib.lib().surf_bn_train_affine(_p(x), n, C, _p(bn.weight.detach()), _p(bn.bias.detach()), float(bn.eps), momentum,
-                                         _p(bn.running_mean if track else None), _p(bn.running_var if track else None),
-                                         _p(scale), _p(shift), _p(stats), _p(ws), _stream())
-    _lib.check(rc, "surf_bn_train_affine")
+    _lib.lib().surf_bn_train_affine(_p(x), n, C, _p(bn.weight.detach()), _p(bn.bias.detach()), float(bn.eps), momentum,
+                                    _p(bn.running_mean if track else None), _p(bn.running_var if track else None),
+                                    _p(scale), _p(shift), _p(stats), _p(ws), _stream())
     if track:
         if counters is not None:
             counters.append(bn.num_batches_tracked)
@@ -2186,8 +2125,7 @@ def bn_train_relu(x, bn, skip=None, saved=None, counters=None, shadow=False):
     if saved is not None:
         saved.update(scale=scale, shift=shift, stats=stats)
     out16 = torch.empty(n, C, dtype=torch.int16, device=dev) if shadow else None     # shadow: the rows' bf16 copy (ops.bf16_rows)
-    _lib.check(_lib.lib().surf_bn_relu_apply16(_p(x), n, C, _p(scale), _p(shift), _p(skip), _p(out), _p(out16), _stream()),
-               "surf_bn_relu_apply16")
+    _lib.lib().surf_bn_relu_apply16(_p(x), n, C, _p(scale), _p(shift), _p(skip), _p(out), _p(out16), _stream())
     if shadow:
         out._rows16 = out16
     return out
@@ -2209,9 +2147,8 @@ def bn_relu_backward(x, dy, scale, shift, stats, train=True, shadow=False):
     ws = torch.empty(_lib.lib().surf_bn_workspace_bytes(C), dtype=torch.uint8, device=dev)
     mean, invstd = stats[:C], stats[C:]
     dx16 = torch.empty(n, C, dtype=torch.int16, device=dev) if shadow else None
-    rc = _lib.lib().surf_bn_relu_backward16(_p(x), _p(dy), n, C, _p(scale), _p(shift), _p(mean), _p(invstd), int(bool(train)),
-                                            _p(ws), _p(dgamma), _p(dbeta), _p(dx), _p(dx16), _stream())
-    _lib.check(rc, "surf_bn_relu_backward16")
+    _lib.lib().surf_bn_relu_backward16(_p(x), _p(dy), n, C, _p(scale), _p(shift), _p(mean), _p(invstd), int(bool(train)),
+                                       _p(ws), _p(dgamma), _p(dbeta), _p(dx), _p(dx16), _stream())
     if shadow:
         dx._rows16 = dx16
     return dx, dgamma, dbeta
@@ -2222,7 +2159,7 @@ def row_linear8(x, weight):
     _chk(weight, torch.float32, "weight")
     assert x.shape[1] == 8 and tuple(weight.shape) == (8, 8)
     out = torch.empty_like(x)
-    _lib.check(_lib.lib().surf_row_linear8(_p(x), _p(weight), x.shape[0], _p(out), _stream()), "surf_row_linear8")
+    _lib.lib().surf_row_linear8(_p(x), _p(weight), x.shape[0], _p(out), _stream())
     return out
 
 
@@ -2238,8 +2175,7 @@ def conv3x3(x, w_packed, cout, stride=1, precision=0):
     _chk(w_packed, torch.float32, "weight")
     N, H, W, cin = x.shape
     out = torch.empty(N, H // stride, W // stride, cout, dtype=torch.float32, device=x.device)
-    rc = _lib.lib().surf_conv3x3_p(_p(x), _p(w_packed), N, H, W, cin, cout, stride, _p(out), int(precision), _stream())
-    _lib.check(rc, f"surf_conv3x3({cin}->{cout}, stride {stride})")
+    _lib.lib().surf_conv3x3_p(_p(x), _p(w_packed), N, H, W, cin, cout, stride, _p(out), int(precision), _stream())
     return out
 
 
@@ -2248,8 +2184,7 @@ def deconv3x3_s2(x, w_packed, cout, precision=0):
     _chk(w_packed, torch.float32, "weight")
     N, H, W, cin = x.shape
     out = torch.empty(N, 2 * H, 2 * W, cout, dtype=torch.float32, device=x.device)
-    rc = _lib.lib().surf_deconv3x3_s2_p(_p(x), _p(w_packed), N, H, W, cin, cout, _p(out), int(precision), _stream())
-    _lib.check(rc, f"surf_deconv3x3_s2({cin}->{cout})")
+    _lib.lib().surf_deconv3x3_s2_p(_p(x), _p(w_packed), N, H, W, cin, cout, _p(out), int(precision), _stream())
     return out
 
 
@@ -2263,8 +2198,7 @@ def conv3x3_wgrad(big, small, stride=1, precision=0):
     assert tuple(big.shape[:3]) == (N, Hs * stride, Ws * stride)
     ws = torch.empty(_lib.lib().surf_conv3x3_wgrad_workspace_floats(N, Hs, Ws, cb, cs), dtype=torch.float32, device=big.device)
     out = torch.empty(3, 3, cb, cs, dtype=torch.float32, device=big.device)
-    rc = _lib.lib().surf_conv3x3_wgrad_p(_p(big), _p(small), N, Hs, Ws, cb, cs, int(stride), _p(ws), _p(out), int(precision), _stream())
-    _lib.check(rc, f"surf_conv3x3_wgrad({cb}x{cs}, stride {stride})")
+    _lib.lib().surf_conv3x3_wgrad_p(_p(big), _p(small), N, Hs, Ws, cb, cs, int(stride), _p(ws), _p(out), int(precision), _stream())
     return out
 
 
@@ -2281,8 +2215,7 @@ def inorm_relu_backward(raw, dy, stats):
         raise ValueError(f"inorm_relu_backward: C = {C} channels; instantiated for C in (8, 16, 32, 64)")
     dx = torch.empty_like(raw)
     ws = torch.empty(_lib.lib().surf_inorm_backward_workspace_bytes(N, C), dtype=torch.uint8, device=raw.device)
-    rc = _lib.lib().surf_inorm_relu_backward(_p(raw), _p(dy), N, H * W, C, _p(stats), _p(ws), _p(dx), _stream())
-    _lib.check(rc, "surf_inorm_relu_backward")
+    _lib.lib().surf_inorm_relu_backward(_p(raw), _p(dy), N, H * W, C, _p(stats), _p(ws), _p(dx), _stream())
     return dx
 
 
@@ -2297,8 +2230,7 @@ def inorm_relu_(x, skip=None, want_stats=False, in_place=True):
     ws = torch.empty(_lib.lib().surf_inorm_workspace_doubles(N, H, W, C), dtype=torch.float64, device=x.device)
     stats = torch.empty(N, C, 2, dtype=torch.float32, device=x.device)
     out = x if in_place else torch.empty_like(x)
-    _lib.check(_lib.lib().surf_inorm_relu_out(_p(x), N, H, W, C, _p(skip), _p(ws), _p(stats), _p(out), _stream()),
-               "surf_inorm_relu_out")
+    _lib.lib().surf_inorm_relu_out(_p(x), N, H, W, C, _p(skip), _p(ws), _p(stats), _p(out), _stream())
     return (out, stats) if want_stats else out
 
 
@@ -2313,8 +2245,7 @@ def occupied_any(pts, volumes):
     out = torch.empty(pts.shape[0], dtype=torch.bool, device=pts.device)
     if pts.shape[0] == 0:
         return out
-    rc = _lib.lib().surf_occupied_any(_p(pts), pts.shape[0], volumes._tp, volumes._dp, volumes.n, _p(out), _stream())
-    _lib.check(rc, "surf_occupied_any")
+    _lib.lib().surf_occupied_any(_p(pts), pts.shape[0], volumes._tp, volumes._dp, volumes.n, _p(out), _stream())
     return out
 
 
@@ -2345,8 +2276,7 @@ def masked_l1(pred, target, mask):
         _l1_counters[key] = torch.zeros(1, dtype=torch.int32, device=dev)
     ws = torch.empty(_lib.lib().surf_masked_l1_workspace_bytes(), dtype=torch.uint8, device=dev)
     out2 = torch.empty(2, dtype=torch.float32, device=dev)
-    rc = _lib.lib().surf_masked_l1(_p(pred), _p(target), _p(m), kind, pred.numel(), _p(ws), _p(_l1_counters[key]), _p(out2), _stream())
-    _lib.check(rc, "surf_masked_l1")
+    _lib.lib().surf_masked_l1(_p(pred), _p(target), _p(m), kind, pred.numel(), _p(ws), _p(_l1_counters[key]), _p(out2), _stream())
     return out2
 
 
@@ -2355,8 +2285,7 @@ def masked_l1_backward(pred, target, mask, out2, upstream):
     m, kind = _l1_mask(mask, pred)
     up = _chk(upstream.reshape(1).float().contiguous(), torch.float32, "upstream")
     g = torch.empty_like(pred)
-    rc = _lib.lib().surf_masked_l1_backward(_p(pred), _p(target), _p(m), kind, pred.numel(), _p(out2), _p(up), _p(g), _stream())
-    _lib.check(rc, "surf_masked_l1_backward")
+    _lib.lib().surf_masked_l1_backward(_p(pred), _p(target), _p(m), kind, pred.numel(), _p(out2), _p(up), _p(g), _stream())
     return g
 
 
@@ -2374,7 +2303,6 @@ def weight_norm_backward(vs, gs, dWs):
     dgs = [torch.empty_like(g) for g in gs]
     rows = (ctypes.c_int * n)(*[int(v.shape[0]) for v in vs])
     cols = (ctypes.c_int * n)(*[int(v.shape[1]) for v in vs])
-    rc = _lib.lib().surf_weight_norm_backward(n, _ptr_array(vs), _ptr_array(gs), _ptr_array(dWs), rows, cols, _ptr_array(dvs),
-                                              _ptr_array(dgs), _stream())
-    _lib.check(rc, "surf_weight_norm_backward")
+    _lib.lib().surf_weight_norm_backward(n, _ptr_array(vs), _ptr_array(gs), _ptr_array(dWs), rows, cols, _ptr_array(dvs),
+                                         _ptr_array(dgs), _stream())
     return dvs, dgs

@@ -315,3 +315,71 @@ def test_masked_l1_host_expression_for_the_three_mask_forms():
     pos = (target > 0).float()
     assert torch.equal(Loss._masked_l1(pred, target, "target>0"), ((pred - target).abs() * pos).sum() / (pos.sum() + 1e-8))
     assert float(Loss._masked_l1(pred, target, torch.zeros(7, 9))) == 0.0
+
+
+def test_binding_signatures_are_derived_from_the_header():
+    """_lib.SIGNATURES and _lib.ABI_VERSION are read from include/surf_hip.h: one entry for every spelling of a parameter or
+    result type the header uses, written out here from the C declarations; no library needed."""
+    import os
+    import re
+    from ctypes import c_double, c_float, c_int, c_int32, c_int64, c_void_p as p
+    from surf_amd import _lib
+    want = {
+        # double and int64_t by value
+        "surf_dtu_cell_keys": (c_int, [p, c_int64, c_double, c_double, c_double, c_double, c_int64, c_int64, c_int64, p, p]),
+        # const float* const*, const uint8_t*, const int32_t*, const int*, float*, void*, int64_t and int by value
+        "surf_sdf_mlp": (c_int, [p, p, p, c_int64, p, p, p, c_int, p, p, p, p, p]),
+        # float by value: inv_s, cos_anneal_ratio, eik_scale
+        "surf_composite_backward_s": (c_int, [p] * 8 + [c_int, c_int, c_float, c_float, p, p, p, c_float] + [p] * 6),
+        # unsigned char*
+        "surf_sdf_pack_weights_bf16": (c_int, [p, p, p]),
+        # int32_t by value (slot0), the header's one use of it
+        "surf_band_assign": (c_int, [p, c_int64, c_int32, p, p, p, p]),
+        # (void) with either result type
+        "surf_sdf_bf16_packed_bytes": (c_int64, []),
+        "surf_blend_raw_floats": (c_int, []),
+    }
+    for name, sig in want.items():
+        assert _lib.SIGNATURES[name] == sig, name
+    with open(os.path.join(os.path.dirname(__file__), "..", "include", "surf_hip.h")) as f:
+        header = f.read()
+    assert _lib.ABI_VERSION == int(re.search(r"#define\s+SURF_ABI_VERSION\s+(\d+)", header).group(1))
+    assert _lib.VALUE_RETURNING <= set(_lib.SIGNATURES)
+    assert all(_lib.SIGNATURES[name][0] is c_int for name in _lib.VALUE_RETURNING)
+
+
+def test_header_parser_refuses_what_it_does_not_understand():
+    """A parameter type outside the mapping, or a declaration the pattern only half matches, raises with the function's name
+    instead of yielding a table with a guessed or missing entry."""
+    from ctypes import c_int, c_void_p
+    from surf_amd import _lib
+    good = "int surf_good(const float* x, int n);  /* a comment, int surf_not_this(long x); */\n"
+    assert _lib.parse_header(good) == {"surf_good": (c_int, [c_void_p, c_int])}
+    with pytest.raises(ValueError, match="surf_bad"):
+        _lib.parse_header(good + "int surf_bad(const float* x,\n             long double y);\n")
+    with pytest.raises(ValueError, match="surf_cb"):                    # a parameter list with parentheses of its own
+        _lib.parse_header(good + "int surf_cb(void (*done)(int), int n);\n")
+    with pytest.raises(ValueError, match="surf_open"):                  # no closing `);`
+        _lib.parse_header(good + "int surf_open(int n\n")
+    with pytest.raises(ValueError, match="surf_unnamed"):               # a bare type: the last word is taken for the name
+        _lib.parse_header(good + "int surf_unnamed(int);\n")
+
+
+def test_status_entry_points_raise_by_themselves():
+    """lib() binds an errcheck to every status-returning entry point: a non-zero status raises SurfHipError with the entry
+    point's own name and its scalar arguments, without any check at the call site; zero is returned unchanged.  The five `int`
+    entry points that return a value are left alone.  Argument validation only: surf_pack_texel4 returns SURF_E_ARG for null
+    pointers before any HIP call, so this runs without a GPU."""
+    from surf_amd import _lib
+    L = _lib.lib()
+    with pytest.raises(_lib.SurfHipError, match="invalid") as e:
+        L.surf_pack_texel4(None, 0, 3, 5, 7, None, None)
+    assert "surf_pack_texel4(0, 3, 5, 7)" in str(e.value)
+    assert L.surf_abi_version() == 41
+    assert L.surf_blend_raw_floats() > 0
+    assert L.surf_blend_packed_floats() > 0
+    assert L.surf_blend_backward_row_floats() > 0
+    assert L.surf_spconv_wgrad_mfma_supported(8, 8) in (0, 1)
+    for name, (res, _) in _lib.SIGNATURES.items():
+        fn = getattr(L, name)
+        assert (fn.errcheck is not None) == (res is _lib.ctypes.c_int and name not in _lib.VALUE_RETURNING), name
