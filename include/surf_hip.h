@@ -823,6 +823,33 @@ int surf_finetune_rays(const void* px, const void* py, int coords_int32, int64_t
 int surf_finetune_gather_pts(const float* pts, int64_t n_pts, const int32_t* idx, int64_t n, float* out, void* stream);
 
 /*
+ * Generalisation training: the batch of one item written on the device from the device-resident DTU training set
+ * (surf_amd/datasets/dtu_resident.py; train_batch.hip).  Added under SURF_ABI_VERSION 41 without a bump, like the entry points
+ * above.  The cache holds uint8 texels (h,w,3), uint8 0/1 masks (h,w) and UNSCALED fp32 depth maps (h,w) on the device;
+ * scaled(d) = (float)((double)d * scale), the rounding of the host reader's `fp32 array * float64 scalar` cast back to fp32.
+ *   surf_train_views: h_images: HOST array of n_views (<= SURF_MAX_VIEWS) device pointers, one image per view slot (a pointer may
+ *     repeat); h_masks / h_depths / h_pseudos: HOST arrays of two device pointers each, the maps of the reference view and of the
+ *     supervised source view (the two may be the same view).  Image and mask pointers 4-byte aligned.  Outputs: imgs
+ *     (n_views,3,h,w) = texel / 256; mask_out (2,h,w) = (float)mask; depth_out / pseudo_out (2,h,w) = scaled(map).  Any h, w.
+ *   surf_train_rays: n_rays rays of the reference view, the n_rays - n_rays / 4 pixels inside its mask first: ray t takes pixel
+ *     inside[pick[t]] (inside: n_inside row-major flat indices y w + x on the device, n_inside <= h w; pick: int32 on the device),
+ *     the last n_rays / 4 rays the pixels (free_x[i], free_y[i]) (int32 on the device; may be NULL when n_rays < 4).  h_kinv (9) =
+ *     inverse(K)[:3,:3] and h_c2w (12) = c2w[:3,:4] of the reference camera, row-major fp32 on the HOST.  Outputs: pixels_x,
+ *     pixels_y (n_rays) = the coordinates as fp32; rays_o, rays_d, color (n_rays,3); depth_out, pseudo_out, mask_out (n_rays).
+ *     color = texel / 256, depth_out / pseudo_out = scaled(map texel), mask_out = (float)mask texel.  A pixel outside the image
+ *     keeps its coordinates and rays and yields zeros for the four gathered entries; a pick outside [0, n_inside) yields zeros
+ *     in every output.  The fp32 operation order of the directions is surf_finetune_rays' and is restated in train_batch.hip's
+ *     header comment.  n_rays <= 2^24.
+ */
+int surf_train_views(const uint8_t* const* h_images, int n_views, int h, int w, const uint8_t* const* h_masks,
+                     const float* const* h_depths, const float* const* h_pseudos, double scale, float* imgs, float* mask_out,
+                     float* depth_out, float* pseudo_out, void* stream);
+int surf_train_rays(const int32_t* pick, const int32_t* free_x, const int32_t* free_y, int n_rays, const int32_t* inside,
+                    int64_t n_inside, const float* h_kinv, const float* h_c2w, const uint8_t* image, const uint8_t* mask,
+                    const float* depth, const float* pseudo, double scale, int h, int w, float* pixels_x, float* pixels_y,
+                    float* rays_o, float* rays_d, float* color, float* depth_out, float* pseudo_out, float* mask_out, void* stream);
+
+/*
  * Per-vertex mesh attributes (ImplicitSurface.vertex_attributes; vertex_attrs.hip): the stages around the SDF gradient and blend
  * kernels, which run unchanged over a mesh's vertex list.  Added under SURF_ABI_VERSION 41 without a bump, like the entry
  * points above.  n >= 2^31 is SURF_E_LIMIT.

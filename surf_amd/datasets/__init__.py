@@ -5,6 +5,7 @@ from torch.utils.data import DataLoader, DistributedSampler, RandomSampler, Sequ
 
 from .dtu import DTUDataset, TanksDataset
 from .dtu_finetune import DTUDatasetFinetune
+from .dtu_resident import DTUDeviceTrainSet
 
 DATASETS = {"DTUDataset": DTUDataset, "TanksDataset": TanksDataset, "DTUDatasetFinetune": DTUDatasetFinetune}
 
@@ -13,9 +14,12 @@ def collect_fn(data):
     return data[0]
 
 
-def get_loader(conf, mode, distributed, num_workers=8):
+def get_loader(conf, mode, distributed, num_workers=8, device=None):
     """datasets/__init__.py:16-43: batch size 1 (one scene + reference view per item), DistributedSampler under DDP;
-    mode "finetune": the dataset itself (runner.py:63), whose get_random_rays / get_rays_at make the batches."""
+    mode "finetune": the dataset itself (runner.py:63), whose get_random_rays / get_rays_at make the batches.
+    device (a GPU; default None = the host reader as it is): in mode "train" a DTUDataset is wrapped in a DTUDeviceTrainSet -
+    the loader then yields device-made batches from the device-resident cache, in this process (num_workers=0), and the third
+    value returned is that set (its `dataset` is the host reader, `stats` the cache's counters)."""
     name = conf.get_string("dataset_name")
     if name not in DATASETS:
         raise NotImplementedError(f"dataset_name {name!r}: surf_amd ships {sorted(DATASETS)} "
@@ -23,6 +27,8 @@ def get_loader(conf, mode, distributed, num_workers=8):
     dataset = DATASETS[name](conf, mode)
     if mode == "finetune":
         return dataset
+    if device is not None and mode == "train" and isinstance(dataset, DTUDataset):
+        dataset, num_workers = DTUDeviceTrainSet(dataset, device), 0
     if distributed:
         sampler = DistributedSampler(dataset, num_replicas=dist.get_world_size(), rank=dist.get_rank())
     else:

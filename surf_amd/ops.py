@@ -1655,6 +1655,82 @@ def finetune_gather_pts(pts, idx):
 
 
 # ------------------------------------------------------------------------------------------------
+# generalisation training (train_batch.hip): the batch of one item from the device-resident training set
+# ------------------------------------------------------------------------------------------------
+
+
+def _chk_plane(t, dtype, shape, name):
+    _chk(t, dtype, name)
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+    if t.data_ptr() % 4:
+        raise ValueError(f"{name}: expected a 4-byte aligned tensor")
+    return t
+
+
+def train_views(images, masks, depths, pseudos, scale):
+    """The per-view planes of one training item.  images: 1..SURF_MAX_VIEWS uint8 (h, w, 3) device tensors, one per view slot (a
+    tensor may repeat); masks / depths / pseudos: two uint8 (h, w) 0/1 masks and two + two fp32 (h, w) unscaled depth maps, those
+    of the reference view and of the supervised source view.  Returns imgs (V, 3, h, w) = texel / 256, masks (2, h, w) fp32 and
+    depths, pseudo depths (2, h, w) = (float)((double)d * scale), the host reader's rounding (train_batch.hip)."""
+    images, masks, depths, pseudos = list(images), list(masks), list(depths), list(pseudos)
+    if not images or len(masks) != 2 or len(depths) != 2 or len(pseudos) != 2:
+        raise ValueError("train_views: at least one image; two masks, two depth maps, two pseudo depth maps")
+    if images[0].dim() != 3:
+        raise ValueError("train_views: images (h, w, 3)")
+    h, w = int(images[0].shape[0]), int(images[0].shape[1])
+    for i, t in enumerate(images):
+        _chk_plane(t, torch.uint8, (h, w, 3), f"images[{i}]")
+    for j in range(2):
+        _chk_plane(masks[j], torch.uint8, (h, w), f"masks[{j}]")
+        _chk_plane(depths[j], torch.float32, (h, w), f"depths[{j}]")
+        _chk_plane(pseudos[j], torch.float32, (h, w), f"pseudos[{j}]")
+    dev = images[0].device
+    imgs = torch.empty(len(images), 3, h, w, dtype=torch.float32, device=dev)
+    mask_out, depth_out, pseudo_out = (torch.empty(2, h, w, dtype=torch.float32, device=dev) for _ in range(3))
+    _lib.lib().surf_train_views(_ptr_array(images), len(images), h, w, _ptr_array(masks), _ptr_array(depths), _ptr_array(pseudos),
+                                float(scale), _p(imgs), _p(mask_out), _p(depth_out), _p(pseudo_out), _stream())
+    return imgs, mask_out, depth_out, pseudo_out
+
+
+def train_rays(pick, free_x, free_y, inside, kinv, c2w, image, mask, depth, pseudo, scale):
+    """The ray block of one training item: len(pick) + len(free_x) rays of the reference view, masked pixels first.  pick (n_masked,)
+    int32 indices into `inside` (n_inside,) int32, the row-major flat indices of the pixels inside the mask; free_x / free_y
+    (n_free,) int32 with n_free = n_rays // 4 - all on the device.  kinv (9 values) = inverse(K)[:3, :3], c2w (12 values) =
+    c2w[:3, :4]: fp32 HOST tensors or arrays.  image (h, w, 3) uint8, mask (h, w) uint8, depth / pseudo (h, w) fp32 unscaled.
+    Returns a dict with pixels_x, pixels_y, rays_o, rays_d, color, depth, pseudo_depth, mask.  The fp32 operation order is the one
+    written out in train_batch.hip."""
+    for t, name in ((pick, "pick"), (free_x, "free_x"), (free_y, "free_y"), (inside, "inside")):
+        _chk(t, torch.int32, name)
+        if t.dim() != 1:
+            raise ValueError(f"train_rays: {name} is a vector")
+    n_masked, n_free = int(pick.shape[0]), int(free_x.shape[0])
+    n = n_masked + n_free
+    if free_y.shape != free_x.shape or n_free != n // 4 or n == 0 or inside.shape[0] == 0:
+        raise ValueError("train_rays: len(free_x) == len(free_y) == n_rays // 4, n_rays = len(pick) + len(free_x) > 0, inside not empty")
+    if image.dim() != 3:
+        raise ValueError("train_rays: image (h, w, 3)")
+    h, w = int(image.shape[0]), int(image.shape[1])
+    _chk_plane(image, torch.uint8, (h, w, 3), "image")
+    _chk_plane(mask, torch.uint8, (h, w), "mask")
+    _chk_plane(depth, torch.float32, (h, w), "depth")
+    _chk_plane(pseudo, torch.float32, (h, w), "pseudo")
+    kinv = np.ascontiguousarray(np.asarray(kinv, dtype=np.float32).reshape(-1))
+    c2w = np.ascontiguousarray(np.asarray(c2w, dtype=np.float32).reshape(-1))
+    if kinv.size != 9 or c2w.size != 12:
+        raise ValueError("train_rays: kinv (9 values), c2w (12 values)")
+    dev = image.device
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)                    # noqa: E731
+    out = {"pixels_x": new(n), "pixels_y": new(n), "rays_o": new(n, 3), "rays_d": new(n, 3), "color": new(n, 3), "depth": new(n),
+           "pseudo_depth": new(n), "mask": new(n)}
+    _lib.lib().surf_train_rays(_p(pick), _p(free_x) if n_free else None, _p(free_y) if n_free else None, n, _p(inside),
+                               int(inside.shape[0]), _np_ptr(kinv), _np_ptr(c2w), _p(image), _p(mask), _p(depth), _p(pseudo),
+                               float(scale), h, w, _p(out["pixels_x"]), _p(out["pixels_y"]), _p(out["rays_o"]), _p(out["rays_d"]),
+                               _p(out["color"]), _p(out["depth"]), _p(out["pseudo_depth"]), _p(out["mask"]), _stream())
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # per-vertex mesh attributes (vertex_attrs.hip): the stages around sdf_mlp / blend over a vertex list
 # ------------------------------------------------------------------------------------------------
 
