@@ -864,6 +864,39 @@ int surf_vertex_points(const void* vertices, int is_f64, int64_t n, float* pts, 
 int surf_vertex_finish(const float* grad, const float* color, const uint8_t* n_valid, int64_t n, float* normals, uint8_t* colors,
                        void* stream);
 
+/*
+ * Depth-map fusion (surf_amd/fusion.py; fuse.hip): truncated-signed-distance integration of the depth maps rendered for many
+ * reference views into one world-frame lattice, and the mesh taken from it.  Added under SURF_ABI_VERSION 41 without a bump, like
+ * the entry points above.  State: tsdf, weight (nx,ny,nz) fp32, z contiguous (the layout surf_mc_* read), color (nx,ny,nz,3) fp32 or
+ * NULL; the lattice points are (ax[i], ay[j], az[k]) (device arrays of nx / ny / nz coordinates, any spacing).  More lattice points
+ * than 2^31 - 1 blocks of 256, nx > 65535, ny nz >= 2^31, or a depth map of 2^31 / 3 pixels or more, is SURF_E_LIMIT.
+ *   surf_fuse_integrate: updates the state in place with n_views (<= SURF_FUSE_MAX_VIEWS: SURF_E_LIMIT beyond) depth views in ONE
+ *     launch, in the order given.  HOST arrays: h_P (n_views,12) fp32, row-major 3x4 world -> (x z, y z, z) with z in world units
+ *     and x, y in depth-map pixel indices; h_depths / h_images: n_views device pointers to the depth maps (H,W) fp32 and the images
+ *     (H,W,3) fp32 (h_images is read only when color != NULL); h_hw (n_views,2) = (H, W); h_dscale (n_views): depth units -> world
+ *     units.  trunc > 0: the truncation distance in world units.  A point's update by one view is a running mean with weight 1 per
+ *     observation of min((d - z) / trunc, 1), skipped where the point is behind the camera, projects (rounded to the nearest pixel)
+ *     outside the map, meets no measurement (d <= 0, NaN, inf) or lies further than trunc behind it.  The fp32 operation order is
+ *     fixed and written out in fuse.hip's header comment.
+ *   surf_fuse_lattice: u (n) = -tsdf where weight > 0, NaN elsewhere: marching cubes' input (surf_mc_classify_observed).
+ *   surf_fuse_vertex_colors: out (n_vertices,3) uint8 = the colour lattice interpolated along the lattice edge each vertex lies on;
+ *     vertices (n_vertices,3) float64 in lattice-index units (surf_mc_emit's), quantised like surf_vertex_finish's colours.  The
+ *     operation order is written out in fuse.hip's header comment.
+ *   surf_mc_classify_observed (mcubes.hip): surf_mc_classify for a lattice with unobserved (non-finite) points.  An edge bit is
+ *     set only where both end points are finite, a cell's triangle count only where its eight corners are; surf_mc_count and
+ *     surf_mc_emit run unchanged on these flags.  (surf_mc_classify reads a NaN as "outside": observed free space, which is
+ *     "inside", would be closed by a sheet wherever it borders unobserved points - frustum sides, dropped pixels.)  Vertices on an
+ *     edge none of whose cells is fully observed are emitted but referenced by no triangle.
+ */
+#define SURF_FUSE_MAX_VIEWS 16
+int surf_fuse_integrate(float* tsdf, float* weight, float* color, const float* ax, const float* ay, const float* az, int nx, int ny,
+                        int nz, const float* h_P, const float* const* h_depths, const float* const* h_images, const int* h_hw,
+                        const float* h_dscale, int n_views, float trunc, void* stream);
+int surf_mc_classify_observed(const float* u, int nx, int ny, int nz, double isovalue, uint8_t* flags, void* stream);
+int surf_fuse_lattice(const float* tsdf, const float* weight, int64_t n, float* u, void* stream);
+int surf_fuse_vertex_colors(const double* vertices, int64_t n_vertices, const float* color, int nx, int ny, int nz, uint8_t* out,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

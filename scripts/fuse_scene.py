@@ -1,0 +1,173 @@
+#!/usr/bin/env python3
+"""One scene mesh from MANY reference views, as ONE command:
+
+    python scripts/fuse_scene.py --conf confs/surf.conf --ckpt ckpt.pth --data_dir <DTU> --scan 24 --ref_views 23 43 12 ... \
+        --voxel_mm 1.0 --colors [--clean_mesh --dtu_test_dir <DTU_TEST>] [--eval_dir <DTU eval data>]
+
+A `val` forward sees one group of views and returns that group's partial mesh in its own normalised frame.  Here one model is
+loaded once and every reference view gets a `val` forward WITHOUT geometry (ipts["extract_geometry"] = False: no per-group SDF
+lattice), whose rendered depth map (--depth sdf_depth | render_depth) becomes a surf_amd.fusion.DepthView and is integrated into
+one world-frame TSDF lattice (csrc/fuse.hip, 16 views per launch); the forward's outputs are dropped after each view.  Then
+FusionVolume.extract_mesh -> mesh_io.write_ply (<out>/meshes/fused/scan<N>.ply, world frame) -> optionally the DTU evaluation
+protocol's cleaner (evaluation/clean_dtu.py) and evaluation.dtu_eval.evaluate_scan -> one JSON line.
+
+The lattice covers the union of the groups' normalised [-1, 1]^3 boxes (fusion.bounds_from_scale_mats; a first pass over the items
+reads their scale_mats) at --voxel_mm world units per step, or --resolution points along the longest side.
+Measurement harness like scripts/dtu_chamfer.py: one scan per call, no logging framework, no resume logic."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--conf", required=True, help="HOCON conf with `model` and `val_dataset` blocks (the reference's confs/*.conf)")
+    ap.add_argument("--ckpt", default=None, help="checkpoint saved by runner.py (`model` key) - omitted: seeded random weights")
+    ap.add_argument("--data_dir", default=None, help="overrides val_dataset.data_dir")
+    ap.add_argument("--scan", type=int, default=24)
+    ap.add_argument("--ref_views", type=int, nargs="+", default=None, help="reference views to fuse (default: val_dataset.ref_view)")
+    size = ap.add_mutually_exclusive_group()
+    size.add_argument("--voxel_mm", type=float, default=None, help="lattice step in world units (DTU: millimetres)")
+    size.add_argument("--resolution", type=int, default=None, help="lattice points along the longest side of the box (default 256)")
+    ap.add_argument("--trunc_voxels", type=float, default=4.0, help="truncation distance in lattice steps")
+    ap.add_argument("--depth", default="sdf_depth", choices=["sdf_depth", "render_depth"], help="which rendered depth map is fused")
+    ap.add_argument("--colors", action="store_true", help="also fuse color_fine and write red green blue into the PLY")
+    ap.add_argument("--clean_mesh", action="store_true",
+                    help="the DTU evaluation protocol's cleaner on the world-frame mesh (evaluation/clean_dtu.py; needs --dtu_test_dir)")
+    ap.add_argument("--dtu_test_dir", default=None, help="DTU_TEST tree (cameras/, scan<N>/mask/) of --clean_mesh")
+    ap.add_argument("--clean_set", type=int, default=1, choices=[0, 1], help="view set of --clean_mesh")
+    ap.add_argument("--clean_backend", default="host", choices=["host", "device"])
+    ap.add_argument("--eval_dir", default=None, help="DTU evaluation data (ObsMask/, Points/stl/): also report the Chamfer distance")
+    ap.add_argument("--eval_device", default="cpu", choices=["cpu", "gpu"])
+    ap.add_argument("--downsample_density", type=float, default=0.2)
+    ap.add_argument("--patch_size", type=float, default=60)
+    ap.add_argument("--max_dist", type=float, default=20)
+    ap.add_argument("--shuffle_seed", type=int, default=0)
+    ap.add_argument("--out_dir", default="./outputs")
+    ap.add_argument("--sdf_precision", default=None, choices=["f32", "bf16x3", "f16x2"])
+    ap.add_argument("--logit_override", default=None, choices=["sphere"],
+                    help="(tests) replace the U-Nets' matching logits by a sphere-concentrated field, as an untrained model needs")
+    ap.add_argument("--device", default="cuda:0")
+    return ap.parse_args(argv)
+
+
+def run(args, state=None):
+    """Returns the JSON record.  state (dict, tests): receives the live `model`, the FusionVolume `volume` and the final world-frame
+    `vertices` / `triangles` (/ `colors`)."""
+    from surf_amd import conf as C
+    from surf_amd import fusion, mesh_io, synthetic
+    from surf_amd.datasets import get_loader
+    from surf_amd.evaluation import clean_dtu, dtu_eval
+    from surf_amd.surf import SuRF
+
+    dev = torch.device(args.device)
+    if args.clean_mesh and args.dtu_test_dir is None:
+        raise SystemExit("fuse_scene: --clean_mesh needs --dtu_test_dir")
+    cfg = C.parse_file(args.conf)
+    dconf = cfg["val_dataset"]
+    if args.data_dir is not None:
+        dconf["data_dir"] = args.data_dir
+    dconf["scene"] = [f"scan{args.scan}"]
+    if args.ref_views is not None:
+        dconf["ref_view"] = list(args.ref_views)
+    mconf = cfg["model"]
+    if args.sdf_precision is not None:
+        mconf["implicit_surface"]["render"]["sdf_precision"] = args.sdf_precision
+
+    t0 = time.perf_counter()
+    loader, _, dataset = get_loader(dconf, "val", False, num_workers=0)
+    if len(dataset) < 1:
+        raise SystemExit(f"fuse_scene: no validation item for scan{args.scan} under {dconf['data_dir']}")
+    torch.manual_seed(0)
+    model = SuRF(mconf)
+    if args.ckpt is not None:
+        ckpt = torch.load(args.ckpt, map_location="cpu")
+        model.load_state_dict(ckpt["model"] if "model" in ckpt else ckpt, strict=True)
+    model = model.to(dev).eval()
+    if args.logit_override == "sphere":
+        model.logit_override = synthetic.sphere_logit
+    ms = {"load": 1e3 * (time.perf_counter() - t0)}
+
+    # ---- the lattice: the union of the groups' unit boxes in the world frame ----
+    t0 = time.perf_counter()
+    lo, hi = fusion.bounds_from_scale_mats([dataset[i]["scale_mat"] for i in range(len(dataset))])
+    voxel = args.voxel_mm if args.voxel_mm is not None else float((hi - lo).max()) / ((args.resolution or 256) - 1)
+    volume = fusion.FusionVolume((lo, hi, voxel), trunc=args.trunc_voxels * voxel, colors=args.colors, device=dev)
+    ms["lattice"] = 1e3 * (time.perf_counter() - t0)
+
+    def sync():
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+
+    # ---- one forward per reference view; views are integrated 16 per launch ----
+    ms.update(forward=0.0, integrate=0.0)
+    pending = []
+
+    def flush():
+        t0 = time.perf_counter()
+        volume.integrate(pending)
+        sync()
+        ms["integrate"] += 1e3 * (time.perf_counter() - t0)
+        pending.clear()
+
+    for item in loader:
+        t0 = time.perf_counter()
+        inputs = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in item.items()}
+        inputs["extract_geometry"] = False
+        with torch.no_grad():
+            out = model("val", inputs, cos_anneal_ratio=1.0)
+        sync()
+        pending.append(fusion.view_from_val(item, out, depth=args.depth))
+        del out, inputs
+        ms["forward"] += 1e3 * (time.perf_counter() - t0)
+        if len(pending) == 16:
+            flush()
+    if pending:
+        flush()
+
+    t0 = time.perf_counter()
+    mesh = volume.extract_mesh()
+    v, t, colors = mesh[0], mesh[1], (mesh[2] if args.colors else None)
+    ms["extract"] = 1e3 * (time.perf_counter() - t0)
+    if len(t) == 0:
+        raise SystemExit("fuse_scene: the fused lattice has no zero crossing between observed points (empty mesh)")
+    if args.clean_mesh:
+        t0 = time.perf_counter()
+        v, t, kept = clean_dtu.clean_dtu_scan(v, t, args.dtu_test_dir, args.scan, view_set=args.clean_set, backend=args.clean_backend,
+                                              device=dev.type, return_index=True)
+        colors = None if colors is None else colors[kept]
+        ms["clean"] = 1e3 * (time.perf_counter() - t0)
+    t0 = time.perf_counter()
+    mesh_path = os.path.join(args.out_dir, "meshes", "fused", f"scan{args.scan}.ply")
+    mesh_io.write_ply(mesh_path, v, t, colors=colors)
+    ms["write"] = 1e3 * (time.perf_counter() - t0)
+    if state is not None:
+        state.update(model=model, volume=volume, vertices=v, triangles=t, colors=colors)
+    rec = {"scan": args.scan, "views_fused": volume.n_views, "lattice": list(volume.shape), "voxel": voxel, "trunc": volume.trunc,
+           "observed_share": volume.observed_share(), "vertices": int(len(v)), "triangles": int(len(t)), "depth": args.depth,
+           "colors": bool(args.colors), "cleaned": bool(args.clean_mesh), "mesh": mesh_path, "ms": ms}
+    if args.eval_dir is not None:
+        t0 = time.perf_counter()
+        d2s, s2d, overall = dtu_eval.evaluate_scan(mesh_path, args.eval_dir, args.scan, patch_size=args.patch_size,
+                                                   max_dist=args.max_dist, downsample_density=args.downsample_density,
+                                                   rng=np.random.default_rng(args.shuffle_seed), device=args.eval_device)
+        ms["evaluate"] = 1e3 * (time.perf_counter() - t0)
+        rec.update(d2s=d2s, s2d=s2d, chamfer=overall)
+    with open(os.path.join(args.out_dir, f"fused_scan{args.scan}.json"), "w") as f:
+        json.dump(rec, f)
+    return rec
+
+
+def main(argv=None):
+    print(json.dumps(run(parse_args(argv))))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,221 @@
+"""Fusion of the depth maps of many `val` forwards into ONE scene mesh.
+
+A `val` forward returns the mesh that one group of 3-7 views sees, in that group's normalised frame.  A scan has 49 views, a
+Tanks and Temples scene hundreds: the whole object comes from one forward per reference view whose rendered depth map
+(`sdf_depth` / `render_depth`, z-depth in the reference camera) is integrated into a world-frame truncated-signed-distance
+lattice - the standard scene-mesh step of this family of methods (VolRecon, ReTR) - followed by iso-surface extraction.
+
+    vol = FusionVolume((lo, hi, voxel), colors=True)
+    for each reference view:  out = model("val", {**inputs, "extract_geometry": False});  vol.integrate([view_from_val(inputs, out)])
+    vertices, triangles, colors = vol.extract_mesh()             # world frame: mesh_io.write_ply as it is
+
+backend="device": csrc/fuse.hip (16 views per launch, the lattice point's state in registers across them) and the marching
+cubes of csrc/mcubes.hip with the observed-corner rule.  backend="host": the numpy-fp32 mirror of the update sequence written
+out in fuse.hip's header comment, operation by operation - the two give equal arrays.  The mesh step always runs on the GPU.
+"""
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from . import ops
+from .marching_cubes import to_host
+
+DepthView = namedtuple("DepthView", "P depth dscale image", defaults=(None,))
+DepthView.__doc__ = """One depth map to fuse.  P (3, 4): world -> (x z, y z, z), z in world units, x / y in pixel indices of `depth`;
+depth (H, W) fp32 (array or tensor), dscale: depth units -> world units; image (H, W, 3) fp32 or None.  A depth that is 0,
+negative, NaN or inf is no measurement."""
+
+_F32_MAX = np.float32(np.finfo(np.float32).max)
+SKIP_REASONS = ("behind", "outside", "no_measurement", "beyond_trunc")
+
+
+def _np(x, dtype=None):
+    x = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+    return x if dtype is None else np.ascontiguousarray(x, dtype=dtype)
+
+
+def similarity_scale(S):
+    """The scale s of a 4x4 similarity (rotation times uniform scale plus translation)."""
+    return float(abs(np.linalg.det(np.asarray(S, dtype=np.float64)[:3, :3])) ** (1.0 / 3.0))
+
+
+def view_from_val(inputs, outputs, depth="sdf_depth", mask=None):
+    """The DepthView of a `val` item's reference camera.  inputs: the item (intrs, c2ws, scale_mat, imgs); outputs: the forward's
+    (depth maps on the validation lattice (Hl, Wl), color_fine).  depth: "sdf_depth", "render_depth" or an (Hl, Wl) array;
+    mask: bool (Hl, Wl), False = the pixel's depth is dropped.
+    With S = scale_mat (normalised -> world, a similarity of scale s): P = K_lat (s (w2c_ref S^-1))[:3, :4], formed in float64 and
+    rounded to fp32 once, and dscale = s.  K_lat = diag((Wl-1)/(W-1), (Hl-1)/(H-1), 1) K: the validation lattice is
+    linspace(0, W-1, Wl) (datasets.dtu.choose_pixels), not K / level."""
+    d = _np(outputs[depth] if isinstance(depth, str) else depth, np.float32)
+    if d.ndim != 2:
+        raise ValueError("view_from_val: depth (Hl, Wl)")
+    Hl, Wl = d.shape
+    H, W = (int(v) for v in inputs["imgs"].shape[-2:])
+    S = _np(inputs["scale_mat"], np.float64).reshape(4, 4)
+    K = _np(inputs["intrs"], np.float64).reshape(-1, 4, 4)[0, :3, :3]
+    w2c = np.linalg.inv(_np(inputs["c2ws"], np.float64).reshape(-1, 4, 4)[0])
+    s = similarity_scale(S)
+    lat = np.diag([(Wl - 1) / (W - 1) if W > 1 else 1.0, (Hl - 1) / (H - 1) if H > 1 else 1.0, 1.0])
+    P = ((lat @ K) @ (s * (w2c @ np.linalg.inv(S)))[:3, :4]).astype(np.float32)
+    if mask is not None:
+        m = _np(mask)
+        if m.dtype != np.bool_ or m.shape != d.shape:
+            raise ValueError("view_from_val: mask is a bool (Hl, Wl) array")
+        d = np.where(m, d, np.float32(0.0))
+    image = None
+    if "color_fine" in outputs:
+        image = _np(outputs["color_fine"], np.float32).reshape(Hl, Wl, 3)
+    return DepthView(P, d, s, image)
+
+
+def bounds_from_scale_mats(scale_mats):
+    """World-frame axis-aligned box (lo (3,), hi (3,)) of the union of the groups' normalised [-1, 1]^3 boxes."""
+    corners = np.array([[x, y, z, 1.0] for x in (-1, 1) for y in (-1, 1) for z in (-1, 1)])
+    pts = np.concatenate([(corners @ _np(S, np.float64).reshape(4, 4).T)[:, :3] for S in scale_mats])
+    return pts.min(0), pts.max(0)
+
+
+def lattice_axes(lo, hi, voxel):
+    """Three fp32 coordinate arrays lo + i voxel (formed in float64) that cover [lo, hi] per axis."""
+    lo, hi, voxel = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3), float(voxel)
+    if not voxel > 0 or not (hi >= lo).all():
+        raise ValueError("FusionVolume: (lo, hi, voxel) with hi >= lo and voxel > 0")
+    return [(lo[a] + voxel * np.arange(int(np.ceil((hi[a] - lo[a]) / voxel - 1e-9)) + 1)).astype(np.float32) for a in range(3)]
+
+
+def integrate_host(tsdf, weight, color, axes, views, trunc, stats=None):
+    """The update sequence of fuse.hip's header comment in numpy fp32, one operation per operator in its order, over the whole
+    lattice view by view (lattice points are independent, so this is the kernel's per-point loop).  tsdf / weight / color:
+    fp32 arrays updated in place; stats (dict, optional): per skip reason the number of (point, view) pairs it dropped, "updated"
+    the number of pairs integrated."""
+    f32 = np.float32
+    px, py, pz = axes[0][:, None, None], axes[1][None, :, None], axes[2][None, None, :]
+    trunc = f32(trunc)
+    for v in views:
+        P = np.asarray(v.P, dtype=f32).reshape(12)
+        depth = np.asarray(v.depth, dtype=f32)
+        H, W = depth.shape
+        with np.errstate(all="ignore"):
+            cx = ((P[0] * px + P[1] * py) + P[2] * pz) + P[3]
+            cy = ((P[4] * px + P[5] * py) + P[6] * pz) + P[7]
+            cz = ((P[8] * px + P[9] * py) + P[10] * pz) + P[11]
+            front = cz > 0
+            rx, ry = np.rint(cx / cz), np.rint(cy / cz)
+            inside = front & (rx >= 0) & (rx <= f32(W - 1)) & (ry >= 0) & (ry <= f32(H - 1))
+            ix, iy = np.where(inside, rx, 0).astype(np.int64), np.where(inside, ry, 0).astype(np.int64)
+            d = depth[iy, ix] * f32(v.dscale)
+            measured = inside & (d > 0) & (d <= _F32_MAX)
+            diff = d - cz
+            ok = measured & (diff >= -trunc)
+            t = np.minimum(diff / trunc, f32(1.0))
+            wn = weight + f32(1.0)
+            tsdf[...] = np.where(ok, (tsdf * weight + t) / wn, tsdf)
+            if color is not None:
+                img = np.asarray(v.image, dtype=f32)[iy, ix]
+                color[...] = np.where(ok[..., None], (color * weight[..., None] + img) / wn[..., None], color)
+            weight[...] = np.where(ok, wn, weight)
+        if stats is not None:
+            for key, n in zip(SKIP_REASONS + ("updated",), (~front, front & ~inside, inside & ~measured, measured & ~ok, ok)):
+                stats[key] = stats.get(key, 0) + int(n.sum())
+
+
+class FusionVolume:
+    """A dense world-frame TSDF lattice that depth views are integrated into.
+
+    grid: three coordinate arrays (any spacing), or (lo, hi, voxel).  trunc: truncation distance in world units (None: 4 x the
+    largest axis step).  colors: also fuse the views' images.  backend "device" (HIP, state on `device`) or "host" (numpy fp32,
+    equal arrays).  integrate() may be called any number of times with any number of views."""
+
+    def __init__(self, grid, trunc=None, colors=False, backend="device", device=None):
+        if backend not in ("device", "host"):
+            raise ValueError(f"FusionVolume: backend {backend!r} (device or host)")
+        if len(grid) != 3:
+            raise ValueError("FusionVolume: three axis arrays or (lo, hi, voxel)")
+        by_voxel = isinstance(grid[2], (int, float, np.integer, np.floating))
+        axes = lattice_axes(*grid) if by_voxel else [_np(a, np.float32).reshape(-1) for a in grid]
+        if any(len(a) < 1 for a in axes):
+            raise ValueError("FusionVolume: an axis without lattice points")
+        steps = [float(np.abs(np.diff(a.astype(np.float64))).max()) for a in axes if len(a) > 1]
+        if trunc is None:
+            if not steps:
+                raise ValueError("FusionVolume: trunc=None needs an axis with two lattice points")
+            trunc = 4.0 * max(steps)
+        self.trunc = float(np.float32(trunc))
+        if not (self.trunc > 0 and np.isfinite(self.trunc)):
+            raise ValueError("FusionVolume: trunc > 0")
+        self.backend, self.shape, self.n_views = backend, tuple(len(a) for a in axes), 0
+        self.axes_host = axes
+        if backend == "device":
+            if not torch.cuda.is_available():
+                raise RuntimeError("FusionVolume(backend='device') needs a GPU (the SuRF hot path has no CPU fallback)")
+            self.device = torch.device("cuda" if device is None else device)
+            self.axes = [torch.from_numpy(a).to(self.device) for a in axes]
+            self.tsdf = torch.zeros(self.shape, dtype=torch.float32, device=self.device)
+            self.weight = torch.zeros(self.shape, dtype=torch.float32, device=self.device)
+            self.color = torch.zeros(self.shape + (3,), dtype=torch.float32, device=self.device) if colors else None
+        else:
+            self.device = None if device is None else torch.device(device)
+            self.axes = axes
+            self.tsdf, self.weight = np.zeros(self.shape, np.float32), np.zeros(self.shape, np.float32)
+            self.color = np.zeros(self.shape + (3,), np.float32) if colors else None
+
+    def _dev(self, x):
+        if torch.is_tensor(x):
+            return x.to(self.device, torch.float32).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(self.device)
+
+    def integrate(self, views, stats=None):
+        """Fuses `views` (DepthViews) in order; on the device 16 per launch.  stats: integrate_host's counters (host backend)."""
+        views = [v if isinstance(v, DepthView) else DepthView(*v) for v in views]
+        if self.color is not None and any(v.image is None for v in views):
+            raise ValueError("FusionVolume.integrate: colours are fused but a view has no image")
+        if self.backend == "host":
+            host = [DepthView(_np(v.P, np.float32), _np(v.depth, np.float32), float(v.dscale),
+                              None if v.image is None else _np(v.image, np.float32)) for v in views]
+            integrate_host(self.tsdf, self.weight, self.color, self.axes, host, self.trunc, stats)
+        else:
+            if stats is not None:
+                raise ValueError("FusionVolume.integrate: stats are counted by the host backend")
+            for s in range(0, len(views), ops.FUSE_MAX_VIEWS):
+                batch = [(_np(v.P, np.float32), self._dev(v.depth), float(v.dscale),
+                          None if self.color is None else self._dev(v.image)) for v in views[s:s + ops.FUSE_MAX_VIEWS]]
+                ops.fuse_integrate(self.tsdf, self.weight, self.color, self.axes, batch, self.trunc)
+        self.n_views += len(views)
+
+    def observed_share(self):
+        """Share of the lattice points that at least one view updated."""
+        return float((self.weight > 0).sum()) / float(np.prod(self.shape))
+
+    def extract_mesh(self, isovalue=0.0):
+        """(vertices (V, 3) float64 in the world frame, triangles (F, 3) int64[, colors (V, 3) uint8 when colours are fused]) as
+        numpy arrays: marching cubes at u = -tsdf = isovalue over the cells whose eight corners were observed, one copy to the
+        host.  Runs on the GPU whatever the backend (the host backend's state is uploaded)."""
+        if self.backend == "device":
+            dev, tsdf, weight, color, axes = self.device, self.tsdf, self.weight, self.color, self.axes
+        else:
+            if not torch.cuda.is_available():
+                raise RuntimeError("FusionVolume.extract_mesh: marching cubes runs on the GPU (the SuRF hot path has no CPU fallback)")
+            dev = torch.device("cuda") if self.device is None else self.device
+            tsdf, weight = torch.from_numpy(self.tsdf).to(dev), torch.from_numpy(self.weight).to(dev)
+            color = None if self.color is None else torch.from_numpy(self.color).to(dev)
+            axes = [torch.from_numpy(a).to(dev) for a in self.axes]
+        v, t = ops.marching_cubes(ops.fuse_lattice(tsdf, weight), float(isovalue), observed_only=True)
+        parts = []
+        if color is not None:
+            c = ops.fuse_vertex_colors(v, color).reshape(-1)
+            parts = [torch.cat([c, c.new_zeros((-c.numel()) % 8)]).view(torch.int64)]
+        # lattice-index units -> world: linear along the lattice edge, in float64 (exact for a uniform axis up to its fp32 values)
+        cols = []
+        for a in range(3):
+            ax = axes[a].double()
+            lo = v[:, a].floor().long().clamp_(0, max(len(ax) - 2, 0))
+            hi = (lo + 1).clamp_(max=len(ax) - 1)
+            cols.append(ax[lo] + (ax[hi] - ax[lo]) * (v[:, a] - lo.double()))
+        vw = torch.stack(cols, dim=1) if len(v) else v
+        both = to_host(torch.cat([vw.reshape(-1).view(torch.int64), t.reshape(-1).to(torch.int64)] + parts))
+        nv, nt = vw.numel(), t.numel()
+        out = (both[:nv].view(torch.float64).numpy().reshape(-1, 3), both[nv:nv + nt].numpy().reshape(-1, 3))
+        if color is not None:
+            out += (both[nv + nt:].view(torch.uint8)[:nv].numpy().reshape(-1, 3),)
+        return out

@@ -1780,10 +1780,13 @@ def vertex_scratch_bytes(n, nv, sdf_precision, blend_precision):
     return need
 
 
-def marching_cubes(u, isovalue=0.0):
+def marching_cubes(u, isovalue=0.0, observed_only=False):
     """mcubes.marching_cubes(u, isovalue) (implicit_surface.py:353) on a device lattice u (nx, ny, nz) fp32.
     Returns (vertices (nv, 3) float64, triangles (nt, 3) int32) device tensors, vertices in lattice-index units.
-    Two host syncs size the outputs (number of active lattice points, then vertex / triangle totals)."""
+    Two host syncs size the outputs (number of active lattice points, then vertex / triangle totals).
+    observed_only (ours, for fused lattices: NaN = no view saw the point): surf_mc_classify_observed instead of surf_mc_classify -
+    vertices only on edges with two finite end points, triangles only in cells with eight finite corners - and the vertices that
+    no triangle references (an edge none of whose cells is fully observed) dropped through clean_update_faces."""
     _chk(u, torch.float32, "u")
     assert u.dim() == 3
     nx, ny, nz = (int(v) for v in u.shape)
@@ -1791,7 +1794,7 @@ def marching_cubes(u, isovalue=0.0):
     L = _lib.lib()
     flags = torch.empty(nx * ny * nz, dtype=torch.uint8, device=dev)
     iso = ctypes.c_double(float(isovalue))       # PyMCubes takes the isovalue as a double
-    L.surf_mc_classify(_p(u), nx, ny, nz, iso, _p(flags), _stream())
+    (L.surf_mc_classify_observed if observed_only else L.surf_mc_classify)(_p(u), nx, ny, nz, iso, _p(flags), _stream())
     active = compact(flags)
     m = int(active.shape[0])
     if m == 0:
@@ -1804,7 +1807,94 @@ def marching_cubes(u, isovalue=0.0):
     triangles = torch.empty(n_t, 3, dtype=torch.int32, device=dev)
     vbase = torch.empty(nx * ny * nz, dtype=torch.int32, device=dev)
     L.surf_mc_emit(_p(u), nx, ny, nz, iso, _p(flags), _p(active), m, _p(ws), _p(vbase), _p(vertices), _p(triangles), _stream())
+    if observed_only:
+        return clean_update_faces(vertices, triangles, torch.ones(n_t, dtype=torch.uint8, device=dev))
     return vertices, triangles
+
+
+# ------------------------------------------------------------------------------------------------
+# depth-map fusion (fuse.hip): TSDF integration of rendered depth maps into one world-frame lattice (surf_amd/fusion.py)
+# ------------------------------------------------------------------------------------------------
+
+FUSE_MAX_VIEWS = 16                              # SURF_FUSE_MAX_VIEWS: views per launch of surf_fuse_integrate
+
+
+def _chk_fuse_state(tsdf, weight, color, axes):
+    _chk(tsdf, torch.float32, "tsdf")
+    _chk(weight, torch.float32, "weight")
+    if tsdf.dim() != 3 or weight.shape != tsdf.shape:
+        raise ValueError("fuse: tsdf and weight (nx, ny, nz)")
+    if color is not None:
+        _chk(color, torch.float32, "color")
+        if tuple(color.shape) != tuple(tsdf.shape) + (3,):
+            raise ValueError("fuse: color (nx, ny, nz, 3)")
+    if len(axes) != 3:
+        raise ValueError("fuse: three axis arrays")
+    for a, n, name in zip(axes, tsdf.shape, ("ax", "ay", "az")):
+        _chk(a, torch.float32, name)
+        if tuple(a.shape) != (int(n),):
+            raise ValueError(f"fuse: {name} holds {tuple(a.shape)} coordinates for {int(n)} lattice points")
+
+
+def fuse_integrate(tsdf, weight, color, axes, views, trunc):
+    """One launch of surf_fuse_integrate: the state tsdf / weight (nx, ny, nz) (and color (nx, ny, nz, 3), or None) is updated in
+    place with `views`, at most FUSE_MAX_VIEWS of them, in order.  axes: the three device coordinate arrays of the lattice; a view
+    is (P (12,) or (3, 4) fp32 on the host, depth (H, W) fp32 device tensor, dscale, image (H, W, 3) fp32 device tensor or None);
+    trunc: world units.  The fp32 update sequence is written out in fuse.hip's header comment."""
+    _chk_fuse_state(tsdf, weight, color, axes)
+    n = len(views)
+    if n == 0:
+        return
+    P = np.empty((n, 12), dtype=np.float32)
+    hw = np.empty((n, 2), dtype=np.int32)
+    dscale = np.empty(n, dtype=np.float32)
+    depths, images = [], []
+    for v, (Pv, depth, ds, image) in enumerate(views):
+        _chk(depth, torch.float32, f"views[{v}].depth")
+        if depth.dim() != 2:
+            raise ValueError(f"fuse_integrate: views[{v}].depth (H, W)")
+        P[v] = np.asarray(Pv, dtype=np.float32).reshape(12)
+        hw[v] = depth.shape
+        dscale[v] = ds
+        depths.append(depth)
+        if color is not None:
+            if image is None:
+                raise ValueError(f"fuse_integrate: colours are fused but views[{v}] has no image")
+            _chk(image, torch.float32, f"views[{v}].image")
+            if tuple(image.shape) != tuple(depth.shape) + (3,):
+                raise ValueError(f"fuse_integrate: views[{v}].image (H, W, 3)")
+            images.append(image)
+    nx, ny, nz = (int(v) for v in tsdf.shape)
+    _lib.lib().surf_fuse_integrate(_p(tsdf), _p(weight), _p(color), _p(axes[0]), _p(axes[1]), _p(axes[2]), nx, ny, nz, _np_ptr(P),
+                                   _ptr_array(depths), _ptr_array(images) if images else None, _np_ptr(hw), _np_ptr(dscale), n,
+                                   ctypes.c_float(float(trunc)), _stream())
+
+
+def fuse_lattice(tsdf, weight):
+    """Marching cubes' input of a fused lattice: u = -tsdf where weight > 0, NaN where no view saw the point."""
+    _chk(tsdf, torch.float32, "tsdf")
+    _chk(weight, torch.float32, "weight")
+    if weight.shape != tsdf.shape:
+        raise ValueError("fuse_lattice: tsdf and weight of one shape")
+    u = torch.empty_like(tsdf)
+    if tsdf.numel():
+        _lib.lib().surf_fuse_lattice(_p(tsdf), _p(weight), tsdf.numel(), _p(u), _stream())
+    return u
+
+
+def fuse_vertex_colors(vertices, color):
+    """Colours (V, 3) uint8 of mesh vertices (V, 3) float64 in lattice-index units (marching_cubes' output) from the fused colour
+    lattice (nx, ny, nz, 3): interpolated along the lattice edge the vertex lies on, quantised like vertex_finish's colours."""
+    _chk(vertices, torch.float64, "vertices")
+    _chk(color, torch.float32, "color")
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or color.dim() != 4 or color.shape[3] != 3:
+        raise ValueError("fuse_vertex_colors: vertices (V, 3), color (nx, ny, nz, 3)")
+    n = int(vertices.shape[0])
+    out = torch.empty(n, 3, dtype=torch.uint8, device=vertices.device)
+    if n:
+        nx, ny, nz = (int(v) for v in color.shape[:3])
+        _lib.lib().surf_fuse_vertex_colors(_p(vertices), n, _p(color), nx, ny, nz, _p(out), _stream())
+    return out
 
 
 # ------------------------------------------------------------------------------------------------

@@ -382,8 +382,11 @@ class SuRF(nn.Module):
             near = near.repeat(rays_o.shape[0], 1)
             far = far.repeat(rays_o.shape[0], 1)
         if mode == "val":
+            # ipts["extract_geometry"] = False (ours, like keep_scene and mesh_resolution): images and depth maps only, no lattice
+            # and no mesh - what a fusion run (surf_amd.fusion: N forwards, one scene mesh) asks of every forward
             return isurf.validate(rays_o, rays_d, near, far, scene, ipts["bound_min"], ipts["bound_max"], ipts["hw"],
-                                  cos_anneal_ratio, step, mesh_resolution=int(ipts.get("mesh_resolution", 512)),
+                                  cos_anneal_ratio, step, extract_geometry=bool(ipts.get("extract_geometry", True)),
+                                  mesh_resolution=int(ipts.get("mesh_resolution", 512)),
                                   vertex_attributes=isurf.mesh_vertex_attributes)
         surface = isurf.render_scene(rays_o, rays_d, near, far, scene, cos_anneal_ratio, patch_warp=True, step=step)
         if "pseudo_pts" in ipts:                                            # implicit_surface.py:425-434
