@@ -46,7 +46,16 @@ __device__ __forceinline__ void bilinear_grad(const float* __restrict__ map, int
       const bool ok = (xi >= 0) & (xi < W) & (yi >= 0) & (yi < H);
       c[j][i] = ok ? *reinterpret_cast<const f32x4*>(map + ((int64_t)yi * W + xi) * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
-  v = (c[0][0] * (1.0f - tx) + c[0][1] * tx) * (1.0f - ty) + (c[1][0] * (1.0f - tx) + c[1][1] * tx) * ty;
+  // the value in bilinear_texel4's own arithmetic (tap weight wx * wy, taps summed row by row, absent taps skipped): bit-equal
+  // to what patch_warp writes for the same sample
+  v = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int xi = x0 + i, yi = y0 + j;
+      if ((xi >= 0) & (xi < W) & (yi >= 0) & (yi < H)) v += c[j][i] * ((i ? tx : 1.0f - tx) * (j ? ty : 1.0f - ty));
+    }
   dx = (c[0][1] - c[0][0]) * (1.0f - ty) + (c[1][1] - c[1][0]) * ty;
   dy = (c[1][0] - c[0][0]) * (1.0f - tx) + (c[1][1] - c[0][1]) * tx;
 }

@@ -959,10 +959,11 @@ def patch_warp(pts, grads, maps_t4, cams, patch_size=11):
     return ref, src
 
 
-def photometric_loss(depth, imgs_t4, mask_ref, cams, ref_idx=0, topk=2, return_warp=False, return_state=False):
+def photometric_loss(depth, imgs_t4, mask_ref, cams, ref_idx=0, topk=2, return_warp=False, return_state=False, return_terms=False):
     """compute_ptloss (losses/photometric_loss.py:54-125) of one (H,W) depth map of view ref_idx: scalar tensor.
     imgs_t4 (nv,H,W,4) texel4; cams: ops.Cameras (host matrices).  return_state: (loss, (warp, column sums)) - what
-    photometric_loss_backward would otherwise recompute with a second run of the forward kernel."""
+    photometric_loss_backward would otherwise recompute with a second run of the forward kernel.  return_terms: (loss, warp,
+    terms) with the per-pixel (H,W,8) columns [l1 m, gx mx, gy my, ssim m | m, mx, my, m] the scalar is reduced from."""
     _chk(depth, torch.float32, "depth")
     _chk(imgs_t4, torch.float32, "imgs_t4")
     _chk(mask_ref, torch.float32, "mask_ref")
@@ -977,6 +978,8 @@ def photometric_loss(depth, imgs_t4, mask_ref, cams, ref_idx=0, topk=2, return_w
                                  _np_ptr(cams.c2w), _np_ptr(cams.w2c), _p(warp), _p(terms), _stream())
     t = terms.view(-1, 8).sum(dim=0, dtype=torch.float64)       # columns [l1 m, gx mx, gy my, ssim m | m, mx, my, m]
     loss = (t[:4] / (t[4:] + 1e-8)).sum().float()
+    if return_terms:
+        return loss, warp, terms
     if return_state:
         return loss, (warp, t)
     return (loss, warp) if return_warp else loss
