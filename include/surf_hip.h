@@ -295,8 +295,9 @@ int surf_blend(const float* pts, const uint8_t* mask, const int32_t* idx, int64_
 #define SURF_BLEND_F32 3      /* the same LDS-resident kernel on v_mfma_f32_32x32x2_f32, no operand split */
 int64_t surf_blend_split_packed_bytes(int precision);
 int surf_blend_pack_weights_split(const float* h_raw, unsigned char* h_packed, int precision);
-/* Bytes of device scratch a launch over n points with nv views needs (per-wavefront staging of the per-view inputs of the
- * second pass; stays in L2 / Infinity Cache).  Contents need not be preserved between launches. */
+/* Bytes of device scratch a launch over n points with nv views needs (the launch's tile counter, then per-wavefront staging of
+ * the per-view inputs of the second pass; stays in L2 / Infinity Cache).  Contents need not be preserved between launches: the
+ * entry points zero the counter on the launch stream themselves.  One buffer serves one launch at a time. */
 int64_t surf_blend_split_scratch_bytes(int64_t n_points, int nv);
 int surf_blend_split(const float* pts, const uint8_t* mask, const int32_t* idx, int64_t n, const float* const* h_feats,
                      const int* h_hw, int n_level, const float* imgs, int nv, const float* h_intrs, const float* h_w2c,

@@ -221,9 +221,24 @@ struct BlendArgs {
   const unsigned char* w;  // LDS image (surf_blend_pack_weights_split)
   float* color;
   uint8_t* n_valid;
-  float* scratch;  // per-wavefront staging slots (surf_blend_split_scratch_bytes)
+  float* scratch;  // per-wavefront staging slots (surf_blend_split_scratch_bytes), behind the DEAL_BYTES of the tile counter
+  unsigned long long* next_tile;  // the launch's tile counter (first word of the caller's scratch, zeroed on the launch stream)
   int nv;
 };
+
+// Tiles are dealt on demand.  A wavefront's first tile is its own index; every further one it takes from ONE counter, in runs of
+// consecutive tiles.  Shares by wavefront index (tile w, w + n_waves, ...) left the younger wavefront of every SIMD behind: the
+// issue arbiter serves the oldest wavefront first, the first-dispatched one finished its share at about three quarters of the
+// launch, and its partner ran the last quarter alone, one wave per SIMD, where a tile costs ~16 % more of the SIMD's time than
+// paired.  With shares that follow speed the two finish together.  Run length: 4 tiles from 32 tiles per wavefront on, 2 from
+// 16, else 1.  On the 576 x 800 render (1.7 M tiles in ~31 ms, 2048 wavefronts, ~37 us per tile and wavefront) that is 14
+// dequeues per microsecond on the word, which saturates near 88 per microsecond; a launch short enough for run length 1 makes
+// at most 55 per microsecond for under 0.6 ms.  Nothing crosses samples, so which wavefront evaluates a tile cannot show.
+// Measured on that render: 34.9 -> 31.7 ms (profiles/r07_render_step_ab.txt).
+constexpr int DEAL_BYTES = 256;
+__device__ __forceinline__ int deal_run(int64_t n_tiles, int64_t n_waves) {
+  return n_tiles >= 32 * n_waves ? 4 : n_tiles >= 16 * n_waves ? 2 : 1;
+}
 
 // Phase boundary for the instruction scheduler: without it hipcc hoists the LDS reads (A fragments, bias rows) of later
 // layers far ahead of their use and spills; latency is hidden by the second wavefront of the SIMD instead.
@@ -710,7 +725,7 @@ __global__ __launch_bounds__(WPB * 64, WPB / 4) void blend_split_kernel(BlendArg
   const int64_t n_pts = a.n_dev ? (int64_t)*a.n_dev : a.n;
   const int64_t n_tiles = (n_pts + TILE - 1) / TILE;
   Stage slot;
-  slot.slot = a.scratch + wave_id * slot_floats(NS);
+  slot.slot = a.scratch + DEAL_BYTES / 4 + wave_id * slot_floats(NS);
   slot.lds_v = lds + lds_bytes<P>() + (threadIdx.x >> 6) * (lds_views<P>() * VIEW_BYTES) + lane * 16;
   slot.n_lds = lds_views<P>();
   const float* scal = reinterpret_cast<const float*>(lds + scal_off<P::BB>());
@@ -722,7 +737,18 @@ __global__ __launch_bounds__(WPB * 64, WPB / 4) void blend_split_kernel(BlendArg
   unsigned long long tprev = __builtin_readcyclecounter(), tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   const unsigned long long t_begin = tprev, rt_begin = __builtin_amdgcn_s_memrealtime();
 #endif
-  for (int64_t tile = wave_id; tile < n_tiles; tile += n_waves) {
+  const int run = deal_run(n_tiles, n_waves);
+  int64_t next = wave_id, run_end = wave_id + 1;  // wave-uniform: the next tile of this wavefront's run, and the run's end
+  for (;;) {
+    if (next == run_end) {  // one lane takes the next run from the counter; the rest of the wavefront reads it from that lane
+      unsigned long long got = 0;
+      if (lane == 0) got = atomicAdd(a.next_tile, (unsigned long long)run);
+      const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)got), hi = __builtin_amdgcn_readfirstlane((uint32_t)(got >> 32));
+      next = n_waves + (int64_t)(((unsigned long long)hi << 32) | lo);
+      run_end = next + run;
+    }
+    if (next >= n_tiles) break;
+    const int64_t tile = next++;
     SURF_BT(0);
     const int64_t slot_i = tile * TILE + j;
     const int64_t sc = slot_i < n_pts ? slot_i : n_pts - 1;
@@ -1082,6 +1108,8 @@ int pack_weights(const float* raw, unsigned char* out) {
 template <class P>
 int launch(const BlendArgs& a, hipStream_t st) {
   dim3 grid(grid_blocks(a.n)), block(WPB * 64);
+  // the tile counter starts every launch at zero: set on the launch stream, no device-global state
+  if (hipError_t e = hipMemsetAsync(a.next_tile, 0, sizeof(unsigned long long), st); e != hipSuccess) return (int)e;
   hipLaunchKernelGGL((blend_split_kernel<P>), grid, block, 0, st, a);
   return surf_check_launch();
 }
@@ -1118,7 +1146,7 @@ extern "C" int surf_blend_pack_weights_split(const float* h_raw, unsigned char* 
 
 extern "C" int64_t surf_blend_split_scratch_bytes(int64_t n_points, int nv) {
   if (n_points <= 0 || nv < 2 || nv > SURF_MAX_VIEWS) return 0;
-  return (int64_t)grid_blocks(n_points) * WPB * slot_floats(nv - 1) * (int64_t)sizeof(float);
+  return DEAL_BYTES + (int64_t)grid_blocks(n_points) * WPB * slot_floats(nv - 1) * (int64_t)sizeof(float);
 }
 
 static int blend_split_impl(const float* pts, const uint8_t* mask, const int32_t* idx, int64_t n, const int32_t* d_n,
@@ -1133,6 +1161,7 @@ static int blend_split_impl(const float* pts, const uint8_t* mask, const int32_t
   a.pts = pts; a.mask = mask; a.idx = idx; a.n = n; a.n_dev = d_n; a.imgs = imgs; a.w = (const unsigned char*)blend_w; a.color = color;
   a.n_valid = n_valid;
   a.scratch = (float*)scratch;
+  a.next_tile = (unsigned long long*)scratch;
   a.nv = nv;
   for (int l = 0; l < 4; ++l) {
     if (!h_feats[l]) return SURF_E_ARG;

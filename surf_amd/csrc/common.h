@@ -132,6 +132,17 @@ __device__ __forceinline__ bool occupied_nearest(const int32_t* __restrict__ tab
   return table[((int64_t)xi * D + yi) * D + zi] >= 0;
 }
 
+// Host side of the "occupied at any level" kernels (ray_setup_kernel, occupied_any_kernel): order[] = the n levels by increasing
+// dims (stable), so that a lane tests the small, cache-resident tables first and leaves its loop at the first hit.  The result
+// is an OR over the levels, whatever their order; the levels need not be nested.
+inline void surf_levels_by_dim(const int* dims, int n, int* order) {
+  for (int i = 0; i < n; ++i) {
+    int k = i;
+    for (; k > 0 && dims[order[k - 1]] > dims[i]; --k) order[k] = order[k - 1];
+    order[k] = i;
+  }
+}
+
 // Bilinear fetch of a texel4 map (H,W,4) with zero padding per tap.
 __device__ __forceinline__ f32x4 bilinear_texel4(const float* __restrict__ map, int H, int W, float x, float y) {
   float fx = floorf(x), fy = floorf(y);

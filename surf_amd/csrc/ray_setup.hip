@@ -144,7 +144,9 @@ __global__ __launch_bounds__(256) void ray_setup_kernel(RaySetupArgs a) {
     float mid = z + dist * 0.5f;
     float px = ox + dx * mid, py = oy + dy * mid, pz = oz + dz * mid;
     bool occ = false;
-    for (int v = 0; v < a.n_vol; ++v) occ |= occupied_nearest(a.tables[v], a.dims[v], px, py, pz);
+    // levels by increasing size (surf_ray_setup sorts them): a lane stops at its first hit, and most hits are in the smallest
+    // table.  A miss goes on to the larger tables: the levels are not assumed to be nested.
+    for (int v = 0; v < a.n_vol && !occ; ++v) occ = occupied_nearest(a.tables[v], a.dims[v], px, py, pz);
     if (live) {
       int64_t o = (int64_t)ray * a.S + k;
       if (a.z_vals) a.z_vals[o] = z;
@@ -197,13 +199,15 @@ extern "C" int surf_ray_setup(const float* rays_o, const float* rays_d, const fl
   a.rays_o = rays_o; a.rays_d = rays_d; a.near = near; a.far = far; a.n_rays = n_rays;
   a.mvol = mvol; a.Dm = Dm; a.lin_depth = lin_depth; a.n_depth = n_depth; a.lin_samples = lin_samples;
   a.n_stage = n_stage; a.S = 0; a.sample_dist = sample_dist; a.n_vol = n_vol; a.jitter = jitter;
+  int by_dim[SURF_MAX_STAGES];
+  surf_levels_by_dim(h_dims, n_vol, by_dim);  // the kernel's occupancy test walks the tables smallest first
   for (int s = 0; s < SURF_MAX_STAGES; ++s) {
     a.n_samples[s] = s < n_stage ? h_n_samples[s] : 0;
     a.ranges[s] = s < n_stage ? h_sample_ranges[s] : 0.f;
     a.S += a.n_samples[s];
-    a.tables[s] = s < n_vol ? h_tables[s] : nullptr;
-    a.dims[s] = s < n_vol ? h_dims[s] : 0;
-    if (s < n_vol && (!h_tables[s] || h_dims[s] <= 0)) return SURF_E_ARG;
+    a.tables[s] = s < n_vol ? h_tables[by_dim[s]] : nullptr;
+    a.dims[s] = s < n_vol ? h_dims[by_dim[s]] : 0;
+    if (s < n_vol && (!a.tables[s] || a.dims[s] <= 0)) return SURF_E_ARG;
   }
   if (a.S <= 0) return SURF_E_ARG;
   if (a.S > SURF_MAX_SAMPLES) return SURF_E_LIMIT;

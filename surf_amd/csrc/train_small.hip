@@ -33,7 +33,7 @@ __global__ __launch_bounds__(256) void occupied_any_kernel(OccArgs a) {
   if (i >= a.n) return;
   const float x = a.pts[3 * i], y = a.pts[3 * i + 1], z = a.pts[3 * i + 2];
   bool occ = false;
-  for (int l = 0; l < a.levels; ++l) {
+  for (int l = 0; l < a.levels && !occ; ++l) {  // smallest table first (sorted by the host), out at the first hit
     const int D = a.dim[l];
     // grid_sample 'nearest', align_corners=False: round half to even of the unnormalised coordinate (rintf), inside test on it
     const float gx = rintf(unnorm_acf(x, D)), gy = rintf(unnorm_acf(y, D)), gz = rintf(unnorm_acf(z, D));
@@ -169,9 +169,11 @@ extern "C" int surf_occupied_any(const float* pts, int64_t n, const int32_t* con
   if (n == 0) return 0;
   OccArgs a;
   a.pts = pts; a.n = n; a.levels = levels; a.out = out;
+  int by_dim[MAX_LEVELS];
+  surf_levels_by_dim(h_dims, levels, by_dim);
   for (int l = 0; l < levels; ++l) {
-    if (!h_tables[l] || h_dims[l] < 1) return SURF_E_ARG;
-    a.table[l] = h_tables[l]; a.dim[l] = h_dims[l];
+    if (!h_tables[by_dim[l]] || h_dims[by_dim[l]] < 1) return SURF_E_ARG;
+    a.table[l] = h_tables[by_dim[l]]; a.dim[l] = h_dims[by_dim[l]];
   }
   hipLaunchKernelGGL(occupied_any_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
   return surf_check_launch();
