@@ -97,7 +97,10 @@ int surf_sdf_mlp(const float* pts, const uint8_t* mask, const int32_t* idx, int6
 /*
  * The same evaluation on the 16-bit matrix pipes with fp32 accumulation (surf_amd/csrc/sdf_mlp_split.hip).  Arguments
  * as surf_sdf_mlp; `packed` is the output of the matching surf_sdf_pack_weights_* (…_packed_bytes() bytes, device copy),
- * `scratch` >= …_scratch_bytes(n).
+ * `scratch` >= …_scratch_bytes(n): the launch's round counter (256 bytes; the gradient kernel deals its rounds of 128 samples
+ * to the workgroups on demand), then the per-wavefront slots of the exponent slices and the feature Jacobian.  Contents need
+ * not be preserved between launches: the entry points zero the counter on the launch stream themselves.  Counter and slots
+ * belong to ONE gradient launch at a time: two gradient launches that may run concurrently (different streams) need two buffers.
  *   bf16x3: every fp32 operand is split exactly into three bf16 pieces and six partial products are accumulated
  *           (dropped terms <= 2^-23 per product): fp32-equivalent results.  The packed image is opaque: the kernel works in
  *           units of the softplus exponent (biases and input columns x 100 log2 e, lin6's row 0 x ln 2 / 100, hidden matrices

@@ -1,7 +1,7 @@
 #!/usr/bin/env bash
 # A/B builds of one or more kernel files: scripts/build_variant.sh NAME "-DFLAG=.. ..." ["file1 file2 ..."] -> build_variants/NAME.so
 # (load with SURF_HIP_LIB=$PWD/build_variants/NAME.so; default file: the split SDF kernel, where -DSURF_SDF_TIMING adds the per-phase
-# clocks time_sdf.py prints; blend_split -DSURF_BLEND_TIMING: the blend kernel's phase clocks for time_blend.py)
+# clocks and the per-workgroup start / end stamps time_sdf.py prints; blend_split -DSURF_BLEND_TIMING: the blend kernel's phase clocks for time_blend.py)
 set -euo pipefail
 cd "$(dirname "${BASH_SOURCE[0]}")/.."
 name=$1; flags=${2:-}; srcs=${3:-sdf_mlp_split}

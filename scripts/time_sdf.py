@@ -1,4 +1,6 @@
-"""Time the SDF kernel variants (forward-only vs forward+gradient) on the bench scene's sample points."""
+"""Time the SDF kernel variants (forward-only vs forward+gradient) on the bench scene's sample points (time_sdf.py [H];
+SURF_PREC=f32|bf16x3|f16x2).  With a -DSURF_SDF_TIMING build (scripts/build_variant.sh): per-phase clocks and, for the gradient
+kernel, every workgroup's finish time with a per-XCD table (how far equal shares of rounds finish apart)."""
 import sys, time, torch
 import os; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from surf_amd import synthetic, ops
@@ -41,3 +43,27 @@ for grad in (False, True):
         v = list(buf); tot = sum(v) or 1
         names = ['gather', 'forward', 'tail', 'backward', 'epilogue', 'stage_wait', 'lds_commit', 'barrier']
         print('  phases (3 runs, wave 0 clocks): ' + ', '.join(f'{n} {x/tot:.3f}' for n, x in zip(names, v)) + f'  total/run/block {tot/3/256:.0f} clk')
+    if grad and hasattr(L, fn.replace('phases', 'sdf_wg')):
+        # the last gradient launch, wavefront 0 of every workgroup: s_memrealtime (100 MHz) at start / end, XCC_ID, rounds done
+        wg = (ctypes.c_ulonglong * 1024)()
+        getattr(L, fn.replace('phases', 'sdf_wg'))(wg)
+        nb = min(256, (n_act + 127) // 128)
+        t0 = min(wg[4 * i] for i in range(nb))
+        fin = [(wg[4 * i + 1] - t0) / 100.0 for i in range(nb)]          # us after the first workgroup's start
+        start = [(wg[4 * i] - t0) / 100.0 for i in range(nb)]
+        xcd = [int(wg[4 * i + 2]) for i in range(nb)]
+        rounds = [int(wg[4 * i + 3]) for i in range(nb)]
+        launch = max(fin)
+        mean = sum(fin) / nb
+        print(f"  launch {launch / 1e3:.3f} ms by the stamps ({dt * 1e3:.3f} ms by the host); latest start {max(start):.0f} us; "
+              f"XCC_ID == workgroup % 8 for {sum(x == i % 8 for i, x in enumerate(xcd))} of {nb} workgroups")
+        print(f"  finish / launch: min {min(fin) / launch:.4f}  mean {mean / launch:.4f}  max 1;  last - first finish {launch - min(fin):.0f} us "
+              f"(one round ~ {launch / max(sum(rounds) / nb, 1):.0f} us);  rounds per workgroup: min {min(rounds)}  max {max(rounds)}  total {sum(rounds)}")
+        print(f"  time available to dealing = launch x (1 - mean(finish) / max(finish)) = {(launch - mean) / 1e3:.3f} ms")
+        for x in sorted(set(xcd)):
+            d = [fin[i] / 1e3 for i in range(nb) if xcd[i] == x]
+            r = [rounds[i] for i in range(nb) if xcd[i] == x]
+            print(f"   XCD {x}: {len(d):3d} workgroups, finish min {min(d):.2f}  mean {sum(d) / len(d):.2f}  max {max(d):.2f} ms;  rounds mean {sum(r) / len(r):.1f}")
+        print('  finish / launch of every workgroup (16 per row, workgroup 0 first):')
+        for i in range(0, nb, 16):
+            print('   ' + ' '.join(f'{f / launch:.4f}' for f in fin[i:i + 16]))

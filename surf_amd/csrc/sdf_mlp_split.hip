@@ -28,8 +28,18 @@
 
 namespace {
 
+// Rounds of the gradient kernel are dealt on demand (1) or walked with a fixed stride (0: the A/B arm, scripts/build_variant.sh);
+// see "dealing" at the round loop.
+#ifndef SURF_SDF_DEAL
+#define SURF_SDF_DEAL 1
+#endif
+constexpr int DEAL_BYTES = 256;  // the launch's round counter, in front of the per-wavefront slots of the caller's scratch
+
 #ifdef SURF_SDF_TIMING  // debug builds only: per-phase shader-clock totals of wavefront 0 of every workgroup
 __device__ unsigned long long g_phase[8];
+// ... and of wavefront 0 of workgroups 0..255: s_memrealtime (100 MHz) at its start / end, the XCC_ID of its compute die, rounds done.
+// Written once at the end of the workgroup, read only by surf_debug_sdf_wg (scripts/time_sdf.py).
+__device__ unsigned long long g_swg[256][4];
 #define SURF_T(k)                                                 \
   do {                                                            \
     const unsigned long long now_ = __builtin_readcyclecounter(); \
@@ -664,7 +674,10 @@ __global__ __launch_bounds__(WPB * 64, P::occ(GRAD)) void sdf_mlp_split_kernel(S
   constexpr int NSL = GRAD ? P::LDS_SLICES : 0;
   // ONE LDS object (ring + exponent slices): with a second __shared__ array the compiler's LDS-DMA alias tracking falls
   // back to `s_waitcnt vmcnt(0)` in front of every ds_read (311 of them, kernel 64 -> 98 ms)
-  __shared__ __attribute__((aligned(16))) char lds[NS * slot_bytes<P>() + WPB * NSL * 4096];
+  // (DEAL: behind them the two words through which wavefront 0 hands the next round to the other three, see the round loop)
+  constexpr bool DEAL = SURF_SDF_DEAL && GRAD && !BRICK;
+  constexpr int DEAL_LDS = NS * slot_bytes<P>() + WPB * NSL * 4096;
+  __shared__ __attribute__((aligned(16))) char lds[DEAL_LDS + (DEAL ? 16 : 0)];
   static_assert(NCH % NS == 0 && (!GRAD || NCH - P::CH.n <= MAX_PAD) && NS >= 3, "slot of a chunk = index % ring length");
   Ctx c;
   c.lane = threadIdx.x & 63;
@@ -699,8 +712,40 @@ __global__ __launch_bounds__(WPB * 64, P::occ(GRAD)) void sdf_mlp_split_kernel(S
 #ifdef SURF_SDF_TIMING
   c.tprev = __builtin_readcyclecounter();
   for (int k = 0; k < 8; ++k) c.tacc[k] = 0;
+  const unsigned long long rt_begin = __builtin_amdgcn_s_memrealtime();
+  unsigned long long rounds_done = 0;
 #endif
-  for (int64_t round = blockIdx.x; round < n_rounds; round += gridDim.x) {
+  // Dealing (gradient kernel): a workgroup's first round is its own index; every further one is gridDim.x + the value it takes
+  // from ONE counter (a.next_round, zeroed on the launch stream), and it leaves at the first value >= n_rounds.  Equal shares
+  // (round b, b + gridDim.x, ...) end the launch when the slowest CU has finished its share; the compute dies differ by a few
+  // per cent (profiles/r08_sdf_dealing_ab.txt).  Nothing crosses samples and the scratch slot belongs to the wavefront, not to
+  // the round, so which workgroup evaluates a round cannot show in sdf or grad.  One dequeue per round (~67 us) and workgroup is
+  // ~4 per microsecond on a word that takes ~88 (blend_split.hip): no run lengths.  n_rounds < 2^32 - gridDim.x: the counter has 32 bits
+  // (n < 2^38 points).
+  // The four wavefronts share the weight ring and its barriers, so all of them must take the same round and leave together:
+  //  * lane 0 of wavefront 0 asks ONE ROUND AHEAD, at the head of round k, in front of the gather's first load.  The atomic is
+  //    the oldest vector-memory operation of the round; vmcnt retires in order, so the gather's own wait for its table / row
+  //    loads (issued after it) has retired it too - long before chunk 0's counted wait, which is the first of the round.  An
+  //    older operation does not change what a counted vmcnt(N) leaves in flight (the youngest N), and the other three
+  //    wavefronts, which skip it, only wait more strictly.
+  //  * the same lane publishes the value behind the gather with a plain ds_write to word (k & 1) of lds[DEAL_LDS ..]; every
+  //    wavefront reads that word at the end of round k (ds_read + readfirstlane: the next round is an SGPR value).
+  //  * publish -> read: the write precedes chunk 0's barrier of round k in wavefront 0 (stage_barrier waits lgkmcnt(0) before it
+  //    signals), the reads follow the round's last barrier in every wavefront: > 50 chunk barriers between them.
+  //  * read -> next overwrite of the same word: word (k & 1) is written again behind the gather of round k + 2; wavefront 0 gets
+  //    there only through the > 50 barriers of round k + 1, which every wavefront joins after its read in round k has
+  //    returned (the readfirstlane waits for it).  With ONE word the write of round k + 1 (before any barrier of that round)
+  //    could overtake a late wavefront's read of round k: hence two, alternating.
+  uint32_t parity = 0;
+  for (int64_t round = blockIdx.x; round < n_rounds;) {
+    uint32_t dealt = 0;
+    if (DEAL && threadIdx.x == 0) {
+      // (the address through an opaque per-lane zero: on a uniform address the compiler's atomic optimiser rewrites the operation
+      // into its wave-aggregated form, whose readfirstlane of the result waits vmcnt(0) right here, a memory round trip per round)
+      uint32_t z = 0;
+      asm volatile("" : "+v"(z));
+      dealt = __hip_atomic_fetch_add(a.next_round + z, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     asm volatile("" : "+s"(c.dma_lds));  // not loop-invariant: the DMA addresses of a round are formed where they are used
     asm volatile("" : "+s"(c.wave1024));  // (likewise the wave's share of the scalar offsets)
     const int64_t tile = round * WPB + c.wave;
@@ -760,6 +805,7 @@ __global__ __launch_bounds__(WPB * 64, P::occ(GRAD)) void sdf_mlp_split_kernel(S
       phi[14] = 1.0f;
       local_frags<P>(phi, pf);
     }
+    if (DEAL && threadIdx.x == 0) *reinterpret_cast<uint32_t*>(lds + DEAL_LDS + parity * 4) = dealt;
     SURF_T(0);
 
     // ------------------------------------------------ forward ----------------------------------------------------
@@ -873,11 +919,26 @@ __global__ __launch_bounds__(WPB * 64, P::occ(GRAD)) void sdf_mlp_split_kernel(S
       }
       SURF_T(4);
     }
+#ifdef SURF_SDF_TIMING
+    ++rounds_done;
+#endif
+    if (DEAL) {
+      round = (int64_t)gridDim.x + (uint32_t)__builtin_amdgcn_readfirstlane(*reinterpret_cast<const uint32_t*>(lds + DEAL_LDS + parity * 4));
+      parity ^= 1u;
+    } else {
+      round += gridDim.x;
+    }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last (unused) prefetches must land before the LDS is freed
 #ifdef SURF_SDF_TIMING
   if (threadIdx.x == 0)
     for (int k = 0; k < 8; ++k) atomicAdd(&g_phase[k], c.tacc[k]);
+  if (GRAD && threadIdx.x == 0 && blockIdx.x < 256) {
+    g_swg[blockIdx.x][0] = rt_begin;
+    g_swg[blockIdx.x][1] = __builtin_amdgcn_s_memrealtime();
+    g_swg[blockIdx.x][2] = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11));  // hwreg(HW_REG_XCC_ID, 0, 4)
+    g_swg[blockIdx.x][3] = rounds_done;
+  }
 #endif
 }
 
@@ -1058,6 +1119,13 @@ int launch(const float* pts, const uint8_t* mask, const int32_t* idx, int64_t n,
     if (s < n_vol && h_dims[s] > 1024) return SURF_E_LIMIT;  // 32-bit table indices (gather_features)
   }
   dim3 grid(grid_blocks<P>(n, grad != nullptr)), block(WPB * 64);
+  a.next_round = nullptr;
+  if (grad && SURF_SDF_DEAL) {
+    // the round counter starts every gradient launch at zero: set on the launch stream, no device-global state
+    a.next_round = (uint32_t*)scratch;
+    a.scratch = (float*)((char*)scratch + DEAL_BYTES);
+    if (hipError_t e = hipMemsetAsync(a.next_round, 0, sizeof(uint32_t), (hipStream_t)stream); e != hipSuccess) return (int)e;
+  }
   if (lat && lat->bricks)
     hipLaunchKernelGGL((sdf_mlp_split_kernel<P, false, true>), grid, block, 0, (hipStream_t)stream, a);
   else if (grad)
@@ -1094,7 +1162,7 @@ int launch_bricks(const float* ax, const float* ay, const float* az, int res, co
 template <class P>
 int64_t scratch_bytes(int64_t n_points) {
   if (n_points <= 0) return 0;
-  return (int64_t)grid_blocks<P>(n_points, true) * WPB * SCR_SLOT * sizeof(float);
+  return (SURF_SDF_DEAL ? DEAL_BYTES : 0) + (int64_t)grid_blocks<P>(n_points, true) * WPB * SCR_SLOT * sizeof(float);
 }
 
 }  // namespace
@@ -1102,9 +1170,14 @@ int64_t scratch_bytes(int64_t n_points) {
 #ifdef SURF_SDF_TIMING
 #ifdef SURF_SDF_TU_F16
 #define SURF_DEBUG_PHASES surf_debug_phases_f16
+#define SURF_DEBUG_WG surf_debug_sdf_wg_f16
 #else
 #define SURF_DEBUG_PHASES surf_debug_phases
+#define SURF_DEBUG_WG surf_debug_sdf_wg
 #endif
+extern "C" int SURF_DEBUG_WG(unsigned long long* out) {  // 256 x {start, end, XCC_ID, rounds} of the last gradient launch
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_swg), sizeof(unsigned long long) * 1024) == hipSuccess ? 0 : 100;
+}
 extern "C" int SURF_DEBUG_PHASES(unsigned long long* out, int reset) {
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase), sizeof(unsigned long long) * 8) != hipSuccess) return 100;
   if (reset) {

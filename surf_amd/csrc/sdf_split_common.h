@@ -310,7 +310,8 @@ struct SdfArgs {
   const unsigned char* packed;
   float* sdf;
   float* grad;
-  float* scratch;
+  float* scratch;        // per-wavefront slots (gradient kernel)
+  uint32_t* next_round;  // gradient kernel: the launch's round counter (first word of the caller's scratch) or nullptr
   // lattice mode (pts == nullptr, forward only; surf_sdf_lattice_*): point i = (ax[i / (ny nz)], ay[(i / nz) % ny], az[i % nz]) from
   // the three axis arrays - no point tensor is written or read - and sdf[i] = out_sign * value (extract_geometry's u = -sdf).
   // Brick mode (the kernel's BRICK instantiation; surf_sdf_bricks_*): idx = brick list, lat_ny = lattice points per axis,
