@@ -378,6 +378,14 @@ int surf_costvol(const int32_t* parents, const int32_t* idx, int64_t n, int D, c
  * workspace: surf_compact_workspace_ints(n) int32; idx_out must hold up to n entries. */
 int64_t surf_compact_workspace_ints(int64_t n);
 int surf_compact(const uint8_t* flags, int64_t n, int32_t* workspace, int32_t* idx_out, int32_t* total, void* stream);
+/* The same compaction of an (n_rays, n_samples) ray-major flag array, emitted in the traversal order
+ * (ray / G, s / B, ray % G, s % B) with G = rays_per_block, B = samples_per_block: a 32-entry tile of the list then holds a
+ * few consecutive samples of a few neighbouring rays.  The last ray block may hold fewer than G rays.  idx_out still holds
+ * flat ray-major indices ray * n_samples + s: a permutation of surf_compact's list (G = 1, B = n_samples: the same list);
+ * *total is their number (device int).  Same workspace (of n = n_rays * n_samples) and the same three launches.
+ * G and B must be powers of two and B must divide n_samples (SURF_E_ARG); n + G * n_samples < 2^31 (SURF_E_LIMIT). */
+int surf_compact_blocked(const uint8_t* flags, int64_t n_rays, int64_t n_samples, int rays_per_block, int samples_per_block,
+                         int32_t* workspace, int32_t* idx_out, int32_t* total, void* stream);
 
 /* dst[i, off:off+row_words] = src[idx[i] >> idx_shift, :]  (rows of 32-bit words; idx_shift 3 = row of the parent) */
 int surf_gather_rows(const void* src, const int32_t* idx, int64_t n, int row_words, int idx_shift, int dst_stride_words,

@@ -1,5 +1,6 @@
 """Time the blending kernels alone on the bench scene's sample points (scripts/time_blend.py [H] ; SURF_BLEND=f32|bf16x3|f16x2,
-comma list allowed; SURF_VIEWS=5)."""
+comma list allowed; SURF_VIEWS=5;
+SURF_SAMPLE_BLOCK=G,B: the active samples in blocks of G rays x B samples, render.sample_block)."""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from surf_amd import synthetic, ops
@@ -22,6 +23,10 @@ R = rays_o.shape[0]
 near = near_fars[0, 0].reshape(1, 1).repeat(R, 1).to(dev); far = near_fars[0, 1].reshape(1, 1).repeat(R, 1).to(dev)
 st = ops.ray_setup(rays_o, rays_d, near, far, mvol, scene.sv, n_samples, [1.0, 0.4, 0.1, 0.01], 256)
 act = ops.compact(st["vmask"])
+if os.environ.get('SURF_SAMPLE_BLOCK', '1,0').split(',')[1] != '0':      # G,B: the list in blocks of G rays x B samples
+    G, B = (int(v) for v in os.environ['SURF_SAMPLE_BLOCK'].split(','))
+    idx, cnt = ops.compact_counted(st["vmask"], block=(sum(n_samples), G, B))
+    act = idx[:int(cnt)].contiguous()
 sd = {k: v for k, v in model.state_dict().items()}
 ref = None
 for prec in os.environ.get('SURF_BLEND', 'f32,f32lds,bf16x3,f16x2').split(','):

@@ -1,5 +1,5 @@
 """Time the SDF kernel variants (forward-only vs forward+gradient) on the bench scene's sample points (time_sdf.py [H];
-SURF_PREC=f32|bf16x3|f16x2).  With a -DSURF_SDF_TIMING build (scripts/build_variant.sh): per-phase clocks and, for the gradient
+SURF_PREC=f32|bf16x3|f16x2; SURF_SAMPLE_BLOCK=G,B: the active samples in blocks of G rays x B samples, render.sample_block).  With a -DSURF_SDF_TIMING build (scripts/build_variant.sh): per-phase clocks and, for the gradient
 kernel, every workgroup's finish time with a per-XCD table (how far equal shares of rounds finish apart)."""
 import sys, time, torch
 import os; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -26,10 +26,15 @@ if os.environ.get('SURF_PREC', 'f32') != 'f32':
     sd = {k: v for k, v in model.state_dict().items()}
     sdf_w = ops.sdf_pack_weights_split(sd, dev, 'sdf_network.', os.environ['SURF_PREC'])
 n_act = int(st["vmask"].sum())
+act = ops.compact(st["vmask"])
+if os.environ.get('SURF_SAMPLE_BLOCK', '1,0').split(',')[1] != '0':      # G,B: the list in blocks of G rays x B samples
+    G, B = (int(v) for v in os.environ['SURF_SAMPLE_BLOCK'].split(','))
+    idx, cnt = ops.compact_counted(st["vmask"], block=(sum(n_samples), G, B))
+    act = idx[:int(cnt)].contiguous()
 for grad in (False, True):
     for it in range(3):
         torch.cuda.synchronize(); t0 = time.perf_counter()
-        ops.sdf_mlp(st["pts"], sv, sdf_w, mask=st["vmask"], want_grad=grad)
+        ops.sdf_mlp(st["pts"], sv, sdf_w, mask=st["vmask"], want_grad=grad, active_idx=act)
         torch.cuda.synchronize(); dt = time.perf_counter() - t0
     flop = n_act * (396960 if grad else 198480)
     print(f"grad={grad}: {dt*1e3:.1f} ms, {flop/dt/1e12:.1f} TFLOP/s algorithmic ({flop/dt/1e12/157.3:.3f} of peak), tiles/s {st['pts'].shape[0]/32/dt:.3e}")

@@ -281,6 +281,142 @@ __global__ __launch_bounds__(CP_THREADS) void compact_scatter_kernel(const uint8
     if (bits & (1u << k)) idx_out[pos++] = (int32_t)(base + k);
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Blocked compaction of an (R, S) ray-major flag array (round 9): the same three launches, but the list is emitted in the
+// traversal order (ray / G, s / B, ray % G, s % B), so that a 32-sample tile of the MLP kernels holds a few consecutive samples
+// of a few neighbouring rays.  The entries stay flat ray-major indices: a permutation of surf_compact's list.
+// Traversal position p -> (ray, s): full ray blocks hold G * S positions, the last one gb = R - blk * G <= G rays; inside a
+// block the S / B sample blocks hold gb * B positions each, ray by ray.  G and B are powers of two and B divides S.
+// A thread keeps 16 consecutive positions as 16 / W groups of W = min(B, 16) flags that are contiguous bytes of one ray
+// (their flat index is a multiple of W: one W-byte load where the array is 16-byte aligned).  R * S is a multiple of W, so
+// a group lies inside the array or past its end as a whole.
+// ---------------------------------------------------------------------------------------------------------
+struct CpBlocked {
+  int R, S, G, B, log_b;
+};
+
+struct CpWalk {
+  int blk, gb, sb, g, j;  // ray block, its number of rays, sample block, ray inside the block, sample inside the sample block
+  __device__ __forceinline__ void seek(uint32_t p, const CpBlocked& a) {
+    const uint32_t per_blk = (uint32_t)a.G * (uint32_t)a.S;
+    blk = (int)(p / per_blk);
+    const uint32_t q = p - (uint32_t)blk * per_blk;
+    gb = min(a.G, a.R - blk * a.G);
+    const uint32_t chunk = (uint32_t)gb << a.log_b;
+    sb = (int)(q / chunk);
+    const uint32_t r = q - (uint32_t)sb * chunk;
+    g = (int)(r >> a.log_b);
+    j = (int)(r & (uint32_t)(a.B - 1));
+  }
+  __device__ __forceinline__ int32_t flat(const CpBlocked& a) const { return (blk * a.G + g) * a.S + (sb << a.log_b) + j; }
+  template <int W>
+  __device__ __forceinline__ void step(const CpBlocked& a) {
+    j += W;
+    if (j < a.B) return;
+    j = 0;
+    if (++g < gb) return;
+    g = 0;
+    if ((++sb << a.log_b) < a.S) return;
+    sb = 0;
+    ++blk;
+    gb = min(a.G, a.R - blk * a.G);
+  }
+};
+
+// W consecutive flags as a W-bit mask
+template <int W>
+__device__ __forceinline__ unsigned cp_mask_w(const uint8_t* __restrict__ p, bool aligned) {
+  unsigned bits = 0;
+  if (W >= 4 && aligned) {
+    uint32_t w[W >= 4 ? W / 4 : 1];
+    if constexpr (W == 16) {
+      const uint4 v = *reinterpret_cast<const uint4*>(p);
+      w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    } else if constexpr (W == 8) {
+      const uint2 v = *reinterpret_cast<const uint2*>(p);
+      w[0] = v.x; w[1] = v.y;
+    } else {
+      w[0] = *reinterpret_cast<const uint32_t*>(p);
+    }
+#pragma unroll
+    for (int k = 0; k < W; ++k) bits |= (((w[k >> 2] >> (8 * (k & 3))) & 0xffu) ? 1u : 0u) << k;
+  } else {
+#pragma unroll
+    for (int k = 0; k < W; ++k) bits |= (p[k] ? 1u : 0u) << k;
+  }
+  return bits;
+}
+
+// The thread's 16 traversal positions from `base` on: their flags as a 16-bit mask, and the flat index of each group's first flag
+template <int W>
+__device__ __forceinline__ unsigned cp_blocked_mask16(const uint8_t* __restrict__ flags, int64_t base, int64_t n,
+                                                      const CpBlocked& a, bool aligned, int32_t (&first)[CP_ITEMS / W]) {
+  unsigned bits = 0;
+#pragma unroll
+  for (int k = 0; k < CP_ITEMS / W; ++k) first[k] = 0;
+  if (base >= n) return 0;
+  CpWalk w;
+  w.seek((uint32_t)base, a);
+#pragma unroll
+  for (int k = 0; k < CP_ITEMS / W; ++k) {
+    if (base + k * W < n) {
+      first[k] = w.flat(a);
+      bits |= cp_mask_w<W>(flags + first[k], aligned) << (k * W);
+      w.template step<W>(a);
+    }
+  }
+  return bits;
+}
+
+template <int W>
+__global__ __launch_bounds__(CP_THREADS) void compact_blocked_count_kernel(const uint8_t* __restrict__ flags, int64_t n, CpBlocked a,
+                                                                           int32_t* __restrict__ block_counts, bool aligned) {
+  __shared__ int s_part[CP_THREADS / 64];
+  const int64_t base = (int64_t)blockIdx.x * CP_BLOCK + (int64_t)threadIdx.x * CP_ITEMS;
+  int32_t first[CP_ITEMS / W];
+  int c = __popc(cp_blocked_mask16<W>(flags, base, n, a, aligned, first));
+  c = (int)wave_sum((float)c);
+  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) block_counts[blockIdx.x] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+}
+
+template <int W>
+__global__ __launch_bounds__(CP_THREADS) void compact_blocked_scatter_kernel(const uint8_t* __restrict__ flags, int64_t n, CpBlocked a,
+                                                                             const int32_t* __restrict__ block_offsets,
+                                                                             int32_t* __restrict__ idx_out, bool aligned) {
+  __shared__ int s_part[CP_THREADS / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t base = (int64_t)blockIdx.x * CP_BLOCK + (int64_t)threadIdx.x * CP_ITEMS;
+  int32_t first[CP_ITEMS / W];
+  const unsigned bits = cp_blocked_mask16<W>(flags, base, n, a, aligned, first);
+  const int c = __popc(bits);
+  int incl = c;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    int t = __shfl_up(incl, o);
+    if (lane >= o) incl += t;
+  }
+  if (lane == 63) s_part[wave] = incl;
+  __syncthreads();
+  int wave_off = 0;
+  for (int w = 0; w < wave; ++w) wave_off += s_part[w];
+  int pos = block_offsets[blockIdx.x] + wave_off + incl - c;
+#pragma unroll
+  for (int k = 0; k < CP_ITEMS; ++k)
+    if (bits & (1u << k)) idx_out[pos++] = first[k / W] + (k % W);
+}
+
+template <int W>
+static void compact_blocked_launch(const uint8_t* flags, int64_t n, const CpBlocked& a, int32_t* workspace, int32_t* idx_out,
+                                   int32_t* total, hipStream_t st) {
+  const int nb = (int)((n + CP_BLOCK - 1) / CP_BLOCK);
+  const bool aligned = ((uintptr_t)flags & 15u) == 0;
+  hipLaunchKernelGGL(compact_blocked_count_kernel<W>, dim3(nb), dim3(CP_THREADS), 0, st, flags, n, a, workspace, aligned);
+  hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(1024), 0, st, workspace, nb, total);
+  hipLaunchKernelGGL(compact_blocked_scatter_kernel<W>, dim3(nb), dim3(CP_THREADS), 0, st, flags, n, a, workspace, idx_out, aligned);
+}
+
 // dst[i, 0:w] = src[idx[i] >> shift, 0:w]   (rows of w 32-bit words; shift = 3 selects the parent row)
 __global__ __launch_bounds__(256) void gather_rows_kernel(const uint32_t* __restrict__ src, const int32_t* __restrict__ idx,
                                                           int64_t n, int w, int shift, int dst_stride, int dst_off,
@@ -1021,6 +1157,27 @@ extern "C" int surf_compact(const uint8_t* flags, int64_t n, int32_t* workspace,
   hipLaunchKernelGGL(compact_count_kernel, dim3(nb), dim3(CP_THREADS), 0, st, flags, n, workspace, aligned);
   hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(1024), 0, st, workspace, nb, total);
   hipLaunchKernelGGL(compact_scatter_kernel, dim3(nb), dim3(CP_THREADS), 0, st, flags, n, workspace, idx_out, aligned);
+  return surf_check_launch();
+}
+
+extern "C" int surf_compact_blocked(const uint8_t* flags, int64_t n_rays, int64_t n_samples, int rays_per_block,
+                                    int samples_per_block, int32_t* workspace, int32_t* idx_out, int32_t* total, void* stream) {
+  const int64_t G = rays_per_block, B = samples_per_block;
+  if (!flags || !workspace || !idx_out || !total || n_rays <= 0 || n_samples <= 0) return SURF_E_ARG;
+  if (G <= 0 || B <= 0 || (G & (G - 1)) || (B & (B - 1)) || n_samples % B) return SURF_E_ARG;
+  const int64_t n = n_rays * n_samples;
+  // int32 indices; the walk steps one ray block past the last position
+  if (n_rays > 0x7fffffffLL || n_samples > 0x7fffffffLL || n + G * n_samples > 0x7fffffffLL) return SURF_E_LIMIT;
+  CpBlocked a;
+  a.R = (int)n_rays; a.S = (int)n_samples; a.G = (int)G; a.B = (int)B;
+  a.log_b = 0;
+  while ((1 << a.log_b) < a.B) ++a.log_b;
+  hipStream_t st = (hipStream_t)stream;
+  if (B >= 16) compact_blocked_launch<16>(flags, n, a, workspace, idx_out, total, st);
+  else if (B == 8) compact_blocked_launch<8>(flags, n, a, workspace, idx_out, total, st);
+  else if (B == 4) compact_blocked_launch<4>(flags, n, a, workspace, idx_out, total, st);
+  else if (B == 2) compact_blocked_launch<2>(flags, n, a, workspace, idx_out, total, st);
+  else compact_blocked_launch<1>(flags, n, a, workspace, idx_out, total, st);
   return surf_check_launch();
 }
 

@@ -11,6 +11,7 @@ backward of a training forward is ``backward_render``, which chai
 gradients of the outputs.
 """
 import math
+import os
 
 import numpy as np
 import torch
@@ -182,6 +183,9 @@ MESH_EXTRACTIONS = ("dense", "band")
 # of the isovalue, i.e. it assumes |grad u| <= margin.  Measured maximum of the finite-difference |grad u| on the bench scene's
 # 512^3 lattice: 1.63 (1.44 near the surface; DESIGN.md K13b, scripts/time_mesh_band.py), rounded up
 MESH_BAND_MARGIN = 2.0
+# render.sample_block default [G, B]: a 32-sample tile of the SDF / blend kernels holds B consecutive samples of each of G
+# neighbouring rays instead of 32 samples of one ray (profiles/r09_sample_order_ab.txt)
+SAMPLE_BLOCK = (8, 4)
 
 
 class ImplicitSurface(nn.Module):
@@ -217,6 +221,15 @@ class ImplicitSurface(nn.Module):
             raise ValueError(f"render.mesh_band_margin must be >= 0, got {self.mesh_band_margin!r}")
         # whether a `val` forward also returns per-vertex normals and blended colours of its mesh (vertex_attributes; default off)
         self.mesh_vertex_attributes = bool(confs.get_bool("render.vertex_attributes", False))
+        # order of the active-sample list of an inference render (render_scene): blocks of G neighbouring rays by B consecutive
+        # samples; [1, 0] = ray-major.  The environment variable SURF_SAMPLE_BLOCK=G,B overrides the conf (A/B measurements)
+        blk = confs.get_list("render.sample_block", list(SAMPLE_BLOCK))
+        if os.environ.get("SURF_SAMPLE_BLOCK"):
+            blk = os.environ["SURF_SAMPLE_BLOCK"].split(",")
+        self.sample_block = tuple(int(v) for v in blk)
+        G, B = self.sample_block if len(self.sample_block) == 2 else (0, 0)
+        if G < 1 or G & (G - 1) or B < 0 or B & (B - 1) or (B == 0 and G != 1):
+            raise ValueError(f"render.sample_block must be [G, B] with powers of two ([1, 0]: ray-major), got {list(blk)!r}")
         self._packed = None
         self.kernel_events = None          # bench.py: list receiving (name, start, end) HIP event triples
         self.active_samples_log = None     # bench.py: list receiving the active-sample count of every render call
@@ -282,7 +295,11 @@ class ImplicitSurface(nn.Module):
         `torch.rand([R, 1]) - 0.5` per stage drawn on the CPU generator in the reference's order, so that a seeded run
         reproduces the reference's sample positions for the same ray batch; `jitter` (R, n_stage) overrides the draw.
         patch_warp: also the training outputs ref_gray_val / sampled_gray_val (:217-245, row a15): the 11x11 homography
-        patches of the stacked feature maps around every ray's SDF zero crossing (from match_features once step >= 2)."""
+        patches of the stacked feature maps around every ray's SDF zero crossing (from match_features once step >= 2).
+        render.sample_block = [G, B] (inference with the split kernels, B dividing the samples per ray): the two MLP kernels
+        walk the active samples in blocks of G consecutive rays by B consecutive samples.  That assumes that the rays arrive in
+        pixel order, as validate, SuRF.forward("val") and bench.py pass them, so that consecutive rays are neighbouring pixels;
+        for rays in any other order the block order changes the speed only, never a result."""
         dev = rays_o.device
         self._random_pts = None
         if jitter is None and self.perturb > 0:
@@ -318,7 +335,12 @@ class ImplicitSurface(nn.Module):
                 # ten real SDF values and the graph stays connected.  (Inference outputs do not depend on it.)
                 act = torch.arange(min(10, st["vmask"].numel()), dtype=torch.int32, device=dev)
         else:
-            act, n_act = timed("compact", lambda: ops.compact_counted(st["vmask"]))
+            # the list in blocks of G neighbouring rays by B consecutive samples (render.sample_block): the lanes of a tile's
+            # gathers then share voxels and texels.  No kernel looks across samples, so the order moves no bit of any output
+            S = st["mid_z"].shape[1]
+            G, B = self.sample_block
+            blk = (S, G, B) if B > 0 and S % B == 0 else None
+            act, n_act = timed("compact", lambda: ops.compact_counted(st["vmask"], block=blk))
         side_fwd = None
         if patch_warp:
             # Two branches of a training forward depend on the sample positions alone and meet the rest only in the output

@@ -1130,17 +1130,26 @@ def compact(flags):
     return idx[:int(total.item())]
 
 
-def compact_counted(flags):
+def compact_counted(flags, block=None):
     """compact without the host round trip: (idx (n,) int32 of which the first `count` entries are the ascending indices of
     the set flags, count (1,) int32 ON THE DEVICE).  For consumers that read the count from device memory (sdf_mlp / blend
-    with `active_count`)."""
+    with `active_count`).
+    block = (S, G, B): the flags are an (n / S, S) ray-major array and the same indices come in the traversal order
+    (ray // G, s // B, ray % G, s % B) - blocks of G neighbouring rays by B consecutive samples (surf_compact_blocked;
+    G and B powers of two, B divides S) - instead of ascending."""
     _chk(flags, torch.uint8, "flags")
     n = flags.numel()
     dev = flags.device
     ws = torch.empty(_lib.lib().surf_compact_workspace_ints(n), dtype=torch.int32, device=dev)
     idx = torch.empty(n, dtype=torch.int32, device=dev)
     total = torch.empty(1, dtype=torch.int32, device=dev)
-    _lib.lib().surf_compact(_p(flags), n, _p(ws), _p(idx), _p(total), _stream())
+    if block is None:
+        _lib.lib().surf_compact(_p(flags), n, _p(ws), _p(idx), _p(total), _stream())
+    else:
+        S, G, B = (int(v) for v in block)
+        if S <= 0 or n % S:
+            raise ValueError(f"compact_counted: {n} flags are no whole number of rays of {S} samples")
+        _lib.lib().surf_compact_blocked(_p(flags), n // S, S, G, B, _p(ws), _p(idx), _p(total), _stream())
     return idx, total
 
 
