@@ -909,6 +909,34 @@ int surf_fuse_lattice(const float* tsdf, const float* weight, int64_t n, float* 
 int surf_fuse_vertex_colors(const double* vertices, int64_t n_vertices, const float* color, int nx, int ny, int nz, uint8_t* out,
                             void* stream);
 
+/*
+ * Multi-view geometric consistency of depth maps (surf_amd/fusion.py filter_views; depth_filter.hip): which pixels of a reference
+ * depth map do enough other views agree with?  A pixel is lifted with its depth, projected into a source view, the source's depth
+ * is read there (bilinear over four MEASURED taps), the source point is projected back, and the source agrees when the round trip
+ * ends within px_thresh pixels of the pixel and within rel_thresh (relative) of its depth.  Added under SURF_ABI_VERSION 41
+ * without a bump, like the entry points above.  A depth that is 0, negative, NaN or inf is no measurement, as in surf_fuse_*.
+ *   surf_depth_consistency: ONE launch tests the reference map depth_r (H,W) fp32 (dscale_r: depth units -> world units) against
+ *     n_sources (<= SURF_FUSE_MAX_VIEWS: SURF_E_LIMIT beyond) source maps, in the order given, one thread per reference pixel.
+ *     HOST arrays: h_T (n_sources,24) fp32 = per source A_rs (3x3 row-major), b_rs (3), A_sr (3x3), b_sr (3) with
+ *     A_rs = M_s M_r^-1, b_rs = t_s - A_rs t_r for P = [M | t] (formed in float64, rounded once: fusion.pair_transforms);
+ *     h_depths: n_sources device pointers to the source maps (Hs,Ws) fp32; h_hw (n_sources,2) = (Hs, Ws); h_dscale (n_sources).
+ *     px2 = px_thresh^2 (fp32), rel_thresh: the two thresholds.  count (H,W) int32 and zsum (H,W) fp32 are READ AND WRITTEN: at a
+ *     measured pixel count grows by one and zsum by the back-projected depth per agreeing source, so more than 16 sources are
+ *     further launches with identical results; pixels the launch does not change are not written.  tile_w: the pixels one
+ *     wavefront covers, 64 = 64 consecutive pixels of the flat row-major index, 16 = a 16 x 4 tile, 8 = an 8 x 8 tile (a choice of
+ *     speed only: the results are the same; other values are SURF_E_ARG).  A map of 2^31 pixels or more, a map side above 2^24
+ *     (its largest index is no exact float) or more than 65535 rows of 8-pixel tiles is SURF_E_LIMIT.
+ *   surf_depth_consistency_finish: n pixels -> out_depth (n) fp32 and keep (n) uint8.  keep = measured and count >= min_consistent;
+ *     out_depth = 0 where not kept, depth_r unchanged where kept, or with average != 0 the mean over the reference and its
+ *     agreeing sources ((zsum + d) / (count + 1)) / dscale_r.
+ * The fp32 operation order of both is fixed and written out in depth_filter.hip's header comment.
+ */
+int surf_depth_consistency(const float* depth_r, int H, int W, float dscale_r, const float* h_T, const float* const* h_depths,
+                           const int* h_hw, const float* h_dscale, int n_sources, float px2, float rel_thresh, int32_t* count,
+                           float* zsum, int tile_w, void* stream);
+int surf_depth_consistency_finish(const float* depth_r, float dscale_r, const int32_t* count, const float* zsum, int64_t n,
+                                  int min_consistent, int average, float* out_depth, uint8_t* keep, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,12 +2,14 @@
 """One scene mesh from MANY reference views, as ONE command:
 
     python scripts/fuse_scene.py --conf confs/surf.conf --ckpt ckpt.pth --data_dir <DTU> --scan 24 --ref_views 23 43 12 ... \
-        --voxel_mm 1.0 --colors [--clean_mesh --dtu_test_dir <DTU_TEST>] [--eval_dir <DTU eval data>]
+        --voxel_mm 1.0 --colors [--min_consistent 2] [--clean_mesh --dtu_test_dir <DTU_TEST>] [--eval_dir <DTU eval data>]
 
 A `val` forward sees one group of views and returns that group's partial mesh in its own normalised frame.  Here one model is
 loaded once and every reference view gets a `val` forward WITHOUT geometry (ipts["extract_geometry"] = False: no per-group SDF
 lattice), whose rendered depth map (--depth sdf_depth | render_depth) becomes a surf_amd.fusion.DepthView and is integrated into
-one world-frame TSDF lattice (csrc/fuse.hip, 16 views per launch); the forward's outputs are dropped after each view.  Then
+one world-frame TSDF lattice (csrc/fuse.hip, 16 views per launch); the forward's outputs are dropped after each view.  With
+--min_consistent K > 0 the views are collected first and only the depth pixels that K other views agree with are integrated
+(the cross-view geometric consistency check of fusion.filter_views, csrc/depth_filter.hip: needs no object masks).  Then
 FusionVolume.extract_mesh -> mesh_io.write_ply (<out>/meshes/fused/scan<N>.ply, world frame) -> optionally the DTU evaluation
 protocol's cleaner (evaluation/clean_dtu.py) and evaluation.dtu_eval.evaluate_scan -> one JSON line.
 
@@ -39,6 +41,14 @@ def parse_args(argv=None):
     ap.add_argument("--trunc_voxels", type=float, default=4.0, help="truncation distance in lattice steps")
     ap.add_argument("--depth", default="sdf_depth", choices=["sdf_depth", "render_depth"], help="which rendered depth map is fused")
     ap.add_argument("--colors", action="store_true", help="also fuse color_fine and write red green blue into the PLY")
+    ap.add_argument("--min_consistent", type=int, default=0,
+                    help="fuse only the depth pixels that at least this many other views agree with (fusion.filter_views, "
+                         "csrc/depth_filter.hip; 0: every pixel is fused)")
+    ap.add_argument("--consistency_px", type=float, default=1.0, help="largest round-trip reprojection error of an agreeing view, pixels")
+    ap.add_argument("--consistency_rel", type=float, default=0.01, help="largest relative depth error of an agreeing view")
+    ap.add_argument("--consistency_sources", type=int, default=None,
+                    help="test a view against its N nearest views by optical axis (default: all fused views)")
+    ap.add_argument("--consistency_average", action="store_true", help="a kept depth becomes the mean over its agreeing views")
     ap.add_argument("--clean_mesh", action="store_true",
                     help="the DTU evaluation protocol's cleaner on the world-frame mesh (evaluation/clean_dtu.py; needs --dtu_test_dir)")
     ap.add_argument("--dtu_test_dir", default=None, help="DTU_TEST tree (cameras/, scan<N>/mask/) of --clean_mesh")
@@ -127,7 +137,21 @@ def run(args, state=None):
         pending.append(fusion.view_from_val(item, out, depth=args.depth))
         del out, inputs
         ms["forward"] += 1e3 * (time.perf_counter() - t0)
-        if len(pending) == 16:
+        if len(pending) == 16 and args.min_consistent == 0:
+            flush()
+    filtered = None
+    if args.min_consistent > 0:
+        # ---- every view is there: drop the depths too few other views agree with, then integrate 16 per launch ----
+        t0 = time.perf_counter()
+        filtered = {}
+        near = None if args.consistency_sources is None else fusion.nearest_sources(pending, args.consistency_sources)
+        views = fusion.filter_views(pending, args.min_consistent, args.consistency_px, args.consistency_rel, sources=near,
+                                    average=args.consistency_average, device=dev, stats=filtered)
+        sync()
+        ms["filter"] = 1e3 * (time.perf_counter() - t0)
+        pending.clear()
+        for s in range(0, len(views), 16):
+            pending.extend(views[s:s + 16])
             flush()
     if pending:
         flush()
@@ -153,6 +177,8 @@ def run(args, state=None):
     rec = {"scan": args.scan, "views_fused": volume.n_views, "lattice": list(volume.shape), "voxel": voxel, "trunc": volume.trunc,
            "observed_share": volume.observed_share(), "vertices": int(len(v)), "triangles": int(len(t)), "depth": args.depth,
            "colors": bool(args.colors), "cleaned": bool(args.clean_mesh), "mesh": mesh_path, "ms": ms}
+    if filtered is not None:
+        rec.update(min_consistent=args.min_consistent, kept_share=sum(filtered["kept"]) / max(sum(filtered["measured"]), 1))
     if args.eval_dir is not None:
         t0 = time.perf_counter()
         d2s, s2d, overall = dtu_eval.evaluate_scan(mesh_path, args.eval_dir, args.scan, patch_size=args.patch_size,

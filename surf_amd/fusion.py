@@ -12,6 +12,11 @@ lattice - the standard scene-mesh step of this family of methods (VolRecon, ReTR
 backend="device": csrc/fuse.hip (16 views per launch, the lattice point's state in registers across them) and the marching
 cubes of csrc/mcubes.hip with the observed-corner rule.  backend="host": the numpy-fp32 mirror of the update sequence written
 out in fuse.hip's header comment, operation by operation - the two give equal arrays.  The mesh step always runs on the GPU.
+
+Which pixels go in: filter_views(views, min_consistent) keeps the depths that enough other views agree with - a pixel is lifted,
+projected into another view, that view's depth is read there and projected back; it agrees when the round trip ends within a
+pixel of where it started and within 1 % of the depth (csrc/depth_filter.hip, 16 sources per launch; consistency_host is its
+numpy-fp32 mirror, equal arrays again).  It needs no object masks, unlike the DTU cleaner.
 """
 from collections import namedtuple
 
@@ -118,6 +123,175 @@ def integrate_host(tsdf, weight, color, axes, views, trunc, stats=None):
         if stats is not None:
             for key, n in zip(SKIP_REASONS + ("updated",), (~front, front & ~inside, inside & ~measured, measured & ~ok, ok)):
                 stats[key] = stats.get(key, 0) + int(n.sum())
+
+
+# ---- multi-view geometric consistency: which pixels of the depth maps go into the lattice (csrc/depth_filter.hip) ----
+
+# the thresholds of the reference's models/losses/consistency_loss.py:43-52: a round trip through the other view ends within 1 pixel
+# of where it started and within 1 % (relative) of the depth it started with
+CONSISTENCY_PX = 1.0
+CONSISTENCY_REL = 0.01
+
+
+def _split_P(view):
+    """(M (3, 3), t (3,), M^-1) in float64 of a view's P = [M | t]."""
+    P = _np(view.P, np.float64).reshape(3, 4)
+    return P[:, :3], P[:, 3], np.linalg.inv(P[:, :3])
+
+
+def _pair(r, s):
+    """pair_transforms from two _split_P triples."""
+    (Mr, tr, Mr_inv), (Ms, ts, Ms_inv) = r, s
+    A_rs, A_sr = Ms @ Mr_inv, Mr @ Ms_inv
+    return (A_rs.astype(np.float32), (ts - A_rs @ tr).astype(np.float32), A_sr.astype(np.float32), (tr - A_sr @ ts).astype(np.float32))
+
+
+def pair_transforms(view_r, view_s):
+    """fp32 (A_rs (3, 3), b_rs (3,), A_sr, b_sr): with q = P_r X = (x z, y z, z) of a world point X in view r, A_rs q + b_rs = P_s X,
+    and back with A_sr / b_sr.  A_rs = M_s M_r^-1, b_rs = t_s - A_rs t_r for P = [M | t], formed in float64 and rounded once."""
+    return _pair(_split_P(view_r), _split_P(view_s))
+
+
+def consistency_host(views, r, sources, px_thresh=CONSISTENCY_PX, rel_thresh=CONSISTENCY_REL):
+    """The rule of depth_filter.hip's header comment in numpy fp32, one operation per operator in its order, over the whole map
+    of views[r], source by source (pixels are independent, so this is the kernel's per-pixel loop).  sources: indices into
+    `views`, tested in this order.  Returns (count (H, W) int32, zsum (H, W) fp32)."""
+    f32 = np.float32
+    ref = views[r]
+    depth_r = _np(ref.depth, f32)
+    H, W = depth_r.shape
+    px = f32(px_thresh)
+    px2, rel_thresh = px * px, f32(rel_thresh)
+    count, zsum = np.zeros((H, W), np.int32), np.zeros((H, W), f32)
+    split_r = _split_P(ref)
+
+    def measured(d):
+        return (d > 0) & (d <= _F32_MAX)
+
+    def rows(A, b, x, y, z):
+        return [((A[k, 0] * x + A[k, 1] * y) + A[k, 2] * z) + b[k] for k in range(3)]
+
+    with np.errstate(all="ignore"):
+        d = depth_r * f32(ref.dscale)
+        live = measured(d)
+        yf, xf = (a.astype(f32) for a in np.mgrid[:H, :W])
+        qx, qy, qz = xf * d, yf * d, d
+        for s in sources:
+            src = views[s]
+            depth_s, dscale_s = _np(src.depth, f32), f32(src.dscale)
+            Hs, Ws = depth_s.shape
+            A_rs, b_rs, A_sr, b_sr = _pair(split_r, _split_P(src))
+            ux, uy, uz = rows(A_rs, b_rs, qx, qy, qz)
+            ok = live & (uz > 0)
+            sx, sy = ux / uz, uy / uz
+            ok &= (sx >= 0) & (sx <= f32(Ws - 1)) & (sy >= 0) & (sy <= f32(Hs - 1))
+            x0f, y0f = np.floor(sx), np.floor(sy)
+            fx, fy = sx - x0f, sy - y0f
+            x0, y0 = np.where(ok, x0f, 0).astype(np.int64), np.where(ok, y0f, 0).astype(np.int64)
+            x1, y1 = np.minimum(x0 + 1, Ws - 1), np.minimum(y0 + 1, Hs - 1)
+            d00, d01 = depth_s[y0, x0] * dscale_s, depth_s[y0, x1] * dscale_s
+            d10, d11 = depth_s[y1, x0] * dscale_s, depth_s[y1, x1] * dscale_s
+            ok &= measured(d00) & measured(d01) & measured(d10) & measured(d11)
+            top = d00 + (d01 - d00) * fx
+            bot = d10 + (d11 - d10) * fx
+            ds = top + (bot - top) * fy
+            wx, wy, wz = rows(A_sr, b_sr, sx * ds, sy * ds, ds)
+            ok &= wz > 0
+            ex, ey = wx / wz - xf, wy / wz - yf
+            e2 = ex * ex + ey * ey
+            rel = np.abs(wz - d) / d
+            ok &= (e2 < px2) & (rel < rel_thresh)
+            count += ok
+            zsum[...] = np.where(ok, zsum + wz, zsum)
+    return count, zsum
+
+
+def finish_host(view, count, zsum, min_consistent, average=False):
+    """The finish step of depth_filter.hip's header comment in numpy fp32: (out depth (H, W) fp32, keep (H, W) bool)."""
+    f32 = np.float32
+    depth = _np(view.depth, f32)
+    with np.errstate(all="ignore"):
+        d = depth * f32(view.dscale)
+        keep = (d > 0) & (d <= _F32_MAX) & (count >= min_consistent)
+        value = ((zsum + d) / (count + 1).astype(f32)) / f32(view.dscale) if average else depth
+        return np.where(keep, value, f32(0.0)).astype(f32), keep
+
+
+def nearest_sources(views, n):
+    """Per view the indices of the n other views whose optical axes (the third row of M, normalised, float64) make the smallest
+    angle with its own, nearest first; ties go to the lower index."""
+    axes = np.stack([_np(v.P, np.float64).reshape(3, 4)[2, :3] for v in views])
+    axes /= np.linalg.norm(axes, axis=1, keepdims=True)
+    cos = axes @ axes.T
+    out = []
+    for i in range(len(views)):
+        others = [j for j in range(len(views)) if j != i]
+        out.append(sorted(others, key=lambda j: -cos[i, j])[:n])            # sorted() is stable: equal angles stay in index order
+    return out
+
+
+def filter_views(views, min_consistent, px_thresh=CONSISTENCY_PX, rel_thresh=CONSISTENCY_REL, sources=None, average=False,
+                 backend="device", device=None, stats=None):
+    """The views with the depths dropped (set to 0) that fewer than min_consistent other views agree with: a list of new
+    DepthViews with the same P, dscale and image objects.  sources: None = every other view, or per view the list of the indices
+    it is tested against (nearest_sources), never itself.  average: a kept depth becomes the mean over the view and its agreeing
+    sources.  backend "device" (csrc/depth_filter.hip; every depth map is uploaded once, the new depths stay on `device`) or
+    "host" (consistency_host: equal arrays).  stats (dict, optional): receives "measured" and "kept" (a list of pixel counts per
+    view) and "count_hist" (per view the histogram of count over its measured pixels, len(its sources) + 1 bins).
+    min_consistent = 0 filters nothing: `views` itself is returned."""
+    if backend not in ("device", "host"):
+        raise ValueError(f"filter_views: backend {backend!r} (device or host)")
+    if int(min_consistent) != min_consistent or min_consistent < 0:
+        raise ValueError("filter_views: min_consistent is a count >= 0")
+    if min_consistent == 0:
+        return views
+    views = [v if isinstance(v, DepthView) else DepthView(*v) for v in views]
+    n = len(views)
+    if sources is None:
+        sources = [[s for s in range(n) if s != r] for r in range(n)]
+    if len(sources) != n:
+        raise ValueError("filter_views: sources lists the source views of every view")
+    for r, src in enumerate(sources):
+        if any(int(s) != s or not 0 <= s < n or s == r for s in src):
+            raise ValueError(f"filter_views: sources[{r}] holds indices of other views")
+    on_device = backend == "device"
+    if on_device:
+        if not torch.cuda.is_available():
+            raise RuntimeError("filter_views(backend='device') needs a GPU (the SuRF hot path has no CPU fallback)")
+        dev = torch.device("cuda" if device is None else device)
+        depths = [v.depth.to(dev, torch.float32).contiguous() if torch.is_tensor(v.depth) else
+                  torch.from_numpy(np.ascontiguousarray(v.depth, dtype=np.float32)).to(dev) for v in views]
+        split = [_split_P(v) for v in views]
+    out, tallies = [], []
+    for r, view in enumerate(views):
+        if on_device:
+            ref = (depths[r], float(view.dscale))
+            count = torch.zeros(depths[r].shape, dtype=torch.int32, device=dev)
+            zsum = torch.zeros(depths[r].shape, dtype=torch.float32, device=dev)
+            for c in range(0, len(sources[r]), ops.FUSE_MAX_VIEWS):
+                ops.depth_consistency(ref, [(_pair(split[r], split[s]), depths[s], float(views[s].dscale))
+                                            for s in sources[r][c:c + ops.FUSE_MAX_VIEWS]], count, zsum, px_thresh, rel_thresh)
+            depth, keep = ops.depth_consistency_finish(ref, count, zsum, min_consistent, average)
+            if stats is not None:                              # counted on the device, read back once after the last view
+                is_measured = ops.depth_consistency_finish(ref, count, zsum, 0)[1].bool()
+                tallies.append(torch.cat([is_measured.sum().reshape(1), keep.sum().reshape(1),
+                                          torch.bincount(count[is_measured].long(), minlength=len(sources[r]) + 1)]))
+        else:
+            count, zsum = consistency_host(views, r, sources[r], px_thresh, rel_thresh)
+            depth, keep = finish_host(view, count, zsum, min_consistent, average)
+            if stats is not None:
+                is_measured = finish_host(view, count, zsum, 0)[1]
+                tallies.append(np.concatenate([[is_measured.sum(), keep.sum()],
+                                               np.bincount(count[is_measured], minlength=len(sources[r]) + 1)]))
+        out.append(view._replace(depth=depth))
+    if stats is not None:
+        if on_device and tallies:
+            sizes = [len(t) for t in tallies]
+            tallies = np.split(torch.cat(tallies).cpu().numpy(), np.cumsum(sizes)[:-1])
+        stats["measured"] = [int(t[0]) for t in tallies]
+        stats["kept"] = [int(t[1]) for t in tallies]
+        stats["count_hist"] = [np.asarray(t[2:], dtype=np.int64) for t in tallies]
+    return out
 
 
 class FusionVolume:

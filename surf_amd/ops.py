@@ -1910,6 +1910,79 @@ def fuse_vertex_colors(vertices, color):
 
 
 # ------------------------------------------------------------------------------------------------
+# multi-view geometric consistency of depth maps (depth_filter.hip): which pixels do enough other views agree with
+# ------------------------------------------------------------------------------------------------
+
+# the pixels one wavefront covers: 64 (flat index), 16 (x 4) or 8 (x 8).  16 x 4 and 8 x 8 measure alike, 64 x 1 is 9-15 % slower
+# at 16 sources from 576 x 800 up (profiles/depth_filter.txt)
+DEPTH_FILTER_TILE_W = 16
+
+
+def _chk_consistency_state(depth, count, zsum, what):
+    _chk(depth, torch.float32, f"{what}: ref depth")
+    _chk(count, torch.int32, f"{what}: count")
+    _chk(zsum, torch.float32, f"{what}: zsum")
+    if depth.dim() != 2 or count.shape != depth.shape or zsum.shape != depth.shape:
+        raise ValueError(f"{what}: ref depth, count and zsum (H, W)")
+    if count.device != depth.device or zsum.device != depth.device:
+        raise ValueError(f"{what}: ref depth, count and zsum on one device")
+
+
+def depth_consistency(ref, sources, count, zsum, px_thresh=1.0, rel_thresh=0.01, tile_w=None):
+    """One launch of surf_depth_consistency: the reference map ref = (depth (H, W) fp32 device tensor, dscale) is tested against
+    `sources`, at most FUSE_MAX_VIEWS of them, in order; count (H, W) int32 and zsum (H, W) fp32 are updated in place (a further
+    call with further sources continues them).  A source is (T, depth (Hs, Ws) fp32 device tensor, dscale) with T the 24 fp32
+    values (A_rs, b_rs, A_sr, b_sr) of fusion.pair_transforms(reference, source), as one array or the four.  tile_w: the
+    thread-to-pixel mapping (None: DEPTH_FILTER_TILE_W; the results do not depend on it).  The fp32 operation sequence is written
+    out in depth_filter.hip's header comment."""
+    depth_r, dscale_r = ref
+    _chk_consistency_state(depth_r, count, zsum, "depth_consistency")
+    n = len(sources)
+    if n == 0:
+        return
+    T = np.empty((n, 24), dtype=np.float32)
+    hw = np.empty((n, 2), dtype=np.int32)
+    dscale = np.empty(n, dtype=np.float32)
+    depths = []
+    for s, (Ts, depth, ds) in enumerate(sources):
+        _chk(depth, torch.float32, f"sources[{s}].depth")
+        if depth.dim() != 2 or depth.numel() == 0:
+            raise ValueError(f"depth_consistency: sources[{s}].depth (Hs, Ws)")
+        if depth.device != depth_r.device:
+            raise ValueError(f"depth_consistency: sources[{s}].depth is not on the reference's device")
+        Ts = np.concatenate([np.asarray(p, dtype=np.float32).reshape(-1) for p in Ts]) if isinstance(Ts, (tuple, list)) else \
+            np.asarray(Ts, dtype=np.float32).reshape(-1)
+        if Ts.shape != (24,):
+            raise ValueError(f"depth_consistency: sources[{s}] transforms hold {Ts.size} values, not A_rs, b_rs, A_sr, b_sr = 24")
+        T[s] = Ts
+        hw[s] = depth.shape
+        dscale[s] = ds
+        depths.append(depth)
+    px = np.float32(px_thresh)
+    H, W = (int(v) for v in depth_r.shape)
+    _lib.lib().surf_depth_consistency(_p(depth_r), H, W, ctypes.c_float(float(dscale_r)), _np_ptr(T), _ptr_array(depths),
+                                      _np_ptr(hw), _np_ptr(dscale), n, ctypes.c_float(float(px * px)),
+                                      ctypes.c_float(float(np.float32(rel_thresh))), _p(count), _p(zsum),
+                                      DEPTH_FILTER_TILE_W if tile_w is None else int(tile_w), _stream())
+
+
+def depth_consistency_finish(ref, count, zsum, min_consistent, average=False):
+    """surf_depth_consistency_finish: (out depth (H, W) fp32, keep (H, W) uint8) of the reference map ref = (depth, dscale) from the
+    count / zsum that depth_consistency accumulated: keep = measured and count >= min_consistent; out = 0 where not kept, the
+    input depth where kept, or with `average` the mean over the reference and its agreeing sources."""
+    depth_r, dscale_r = ref
+    _chk_consistency_state(depth_r, count, zsum, "depth_consistency_finish")
+    if int(min_consistent) < 0:
+        raise ValueError("depth_consistency_finish: min_consistent >= 0")
+    out = torch.empty_like(depth_r)
+    keep = torch.empty(depth_r.shape, dtype=torch.uint8, device=depth_r.device)
+    if depth_r.numel():
+        _lib.lib().surf_depth_consistency_finish(_p(depth_r), ctypes.c_float(float(dscale_r)), _p(count), _p(zsum), depth_r.numel(),
+                                                 int(min_consistent), int(bool(average)), _p(out), _p(keep), _stream())
+    return out, keep
+
+
+# ------------------------------------------------------------------------------------------------
 # narrow-band marching cubes (mesh_band.hip): the dense mesh from the SDF in 8^3-cell bricks near the surface
 # ------------------------------------------------------------------------------------------------
 
