@@ -937,6 +937,36 @@ int surf_depth_consistency(const float* depth_r, int H, int W, float dscale_r, c
 int surf_depth_consistency_finish(const float* depth_r, float dscale_r, const int32_t* count, const float* zsum, int64_t n,
                                   int min_consistent, int average, float* out_depth, uint8_t* keep, void* stream);
 
+/*
+ * Fused point clouds (surf_amd/fusion.py fuse_points; point_cloud.hip): the depth maps of many views merged into one cloud with one
+ * point per surface sample.  Views are visited in index order; a pixel that is measured, not yet used and agreed with by at least
+ * min_consistent sources (the rule of surf_depth_consistency) is emitted, and the pixel it lands on in every agreeing source is
+ * marked used, so that it is not emitted again.  Added under SURF_ABI_VERSION 41 without a bump, like the entry points above.
+ * used maps are (H,W) uint8, 0 or 1.  Per view the caller runs surf_points_candidates, surf_depth_consistency (+ _finish) on the
+ * candidates, surf_points_mark per chunk of sources, and surf_points_lift on the ordered list of kept pixels, all on one stream.
+ * Empty work (no pixels, no sources, no kept pixels) returns 0 at once: no zero-sized grid is launched.  A map of 2^31 pixels or
+ * more or a map side above 2^24 is SURF_E_LIMIT, as for surf_depth_consistency.
+ *   surf_points_candidates: out (n) = 0 where used != 0, depth elsewhere: a used pixel is no measurement as a reference.
+ *   surf_points_mark: ONE launch re-runs the rule at the pixels of the reference map cand_r (H,W) with keep != 0 against n_sources
+ *     (<= SURF_FUSE_MAX_VIEWS: SURF_E_LIMIT beyond) sources - h_T, h_depths, h_hw, h_dscale, px2, rel_thresh as for
+ *     surf_depth_consistency - and stores 1 at h_used[s][rintf(sy), rintf(sx)] (HOST array of n_sources device pointers to the
+ *     sources' used maps (Hs,Ws)) for every agreeing source s; (sx, sy) is the pixel's projection into s, inside the map by the
+ *     rule.  No h_used[s] may be the reference's own map.
+ *   surf_points_lift: kept (n_kept) int64 = the flat row-major indices of the kept pixels, ascending.  Per kept pixel k:
+ *     z = average ? (zsum + d) / (count + 1) : d with d = cand_r * dscale_r; points (n_kept,3) fp32 = Minv (x z, y z, z) + c with
+ *     HOST h_lift (12) fp32 = Minv = M^-1 (3x3 row-major) then c = -M^-1 t for P = [M | t] (formed in float64, rounded once);
+ *     colors (n_kept,3) uint8 = image (H,W,3) fp32 at the pixel, quantised like surf_fuse_vertex_colors (image NULL: colors is
+ *     not written); origin (n_kept,2) int32 = (view, flat pixel index).  An index outside the map writes nothing.
+ * The fp32 operation order is fixed and written out in point_cloud.hip's header comment.
+ */
+int surf_points_candidates(const float* depth, const uint8_t* used, int64_t n, float* out, void* stream);
+int surf_points_mark(const float* cand_r, int H, int W, float dscale_r, const uint8_t* keep, const float* h_T,
+                     const float* const* h_depths, uint8_t* const* h_used, const int* h_hw, const float* h_dscale, int n_sources,
+                     float px2, float rel_thresh, void* stream);
+int surf_points_lift(const float* cand_r, int H, int W, float dscale_r, const int32_t* count, const float* zsum, int average,
+                     const int64_t* kept, int64_t n_kept, const float* h_lift, const float* image, int view, float* points,
+                     uint8_t* colors, int32_t* origin, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,8 @@
 """One scene mesh from MANY reference views, as ONE command:
 
     python scripts/fuse_scene.py --conf confs/surf.conf --ckpt ckpt.pth --data_dir <DTU> --scan 24 --ref_views 23 43 12 ... \
-        --voxel_mm 1.0 --colors [--min_consistent 2] [--clean_mesh --dtu_test_dir <DTU_TEST>] [--eval_dir <DTU eval data>]
+        --voxel_mm 1.0 --colors [--min_consistent 2] [--point_cloud] [--clean_mesh --dtu_test_dir <DTU_TEST>] \
+        [--eval_dir <DTU eval data>]
 
 A `val` forward sees one group of views and returns that group's partial mesh in its own normalised frame.  Here one model is
 loaded once and every reference view gets a `val` forward WITHOUT geometry (ipts["extract_geometry"] = False: no per-group SDF
@@ -12,6 +13,9 @@ one world-frame TSDF lattice (csrc/fuse.hip, 16 views per launch); the forward's
 (the cross-view geometric consistency check of fusion.filter_views, csrc/depth_filter.hip: needs no object masks).  Then
 FusionVolume.extract_mesh -> mesh_io.write_ply (<out>/meshes/fused/scan<N>.ply, world frame) -> optionally the DTU evaluation
 protocol's cleaner (evaluation/clean_dtu.py) and evaluation.dtu_eval.evaluate_scan -> one JSON line.
+With --point_cloud the same depth maps are ALSO merged into one point cloud, one point per surface sample (fusion.fuse_points,
+csrc/point_cloud.hip, with the --min_consistent / --consistency_* flags) -> <out>/meshes/fused/scan<N>_points.ply, scored with
+the evaluator's point-cloud mode when --eval_dir is given; the mesh and its fields of the record are what they are without it.
 
 The lattice covers the union of the groups' normalised [-1, 1]^3 boxes (fusion.bounds_from_scale_mats; a first pass over the items
 reads their scale_mats) at --voxel_mm world units per step, or --resolution points along the longest side.
@@ -49,6 +53,9 @@ def parse_args(argv=None):
     ap.add_argument("--consistency_sources", type=int, default=None,
                     help="test a view against its N nearest views by optical axis (default: all fused views)")
     ap.add_argument("--consistency_average", action="store_true", help="a kept depth becomes the mean over its agreeing views")
+    ap.add_argument("--point_cloud", action="store_true",
+                    help="also merge the depth maps into one point cloud (fusion.fuse_points: a pixel that --min_consistent other "
+                         "views agree with is emitted once) and write meshes/fused/scan<N>_points.ply")
     ap.add_argument("--clean_mesh", action="store_true",
                     help="the DTU evaluation protocol's cleaner on the world-frame mesh (evaluation/clean_dtu.py; needs --dtu_test_dir)")
     ap.add_argument("--dtu_test_dir", default=None, help="DTU_TEST tree (cameras/, scan<N>/mask/) of --clean_mesh")
@@ -118,7 +125,7 @@ def run(args, state=None):
 
     # ---- one forward per reference view; views are integrated 16 per launch ----
     ms.update(forward=0.0, integrate=0.0)
-    pending = []
+    pending, cloud_views = [], []
 
     def flush():
         t0 = time.perf_counter()
@@ -135,10 +142,23 @@ def run(args, state=None):
             out = model("val", inputs, cos_anneal_ratio=1.0)
         sync()
         pending.append(fusion.view_from_val(item, out, depth=args.depth))
+        if args.point_cloud:
+            cloud_views.append(pending[-1])
         del out, inputs
         ms["forward"] += 1e3 * (time.perf_counter() - t0)
         if len(pending) == 16 and args.min_consistent == 0:
             flush()
+    cloud = None
+    if args.point_cloud:
+        # ---- every view is there: the consistent depths as one cloud, each surface sample once (the unfiltered maps go in) ----
+        t0 = time.perf_counter()
+        near = None if args.consistency_sources is None else fusion.nearest_sources(cloud_views, args.consistency_sources)
+        cloud = fusion.fuse_points(cloud_views, args.min_consistent, args.consistency_px, args.consistency_rel, sources=near,
+                                   device=dev)
+        ms["points"] = 1e3 * (time.perf_counter() - t0)
+        points_path = os.path.join(args.out_dir, "meshes", "fused", f"scan{args.scan}_points.ply")
+        mesh_io.write_ply_points(points_path, cloud.points, cloud.colors)
+        cloud_views.clear()
     filtered = None
     if args.min_consistent > 0:
         # ---- every view is there: drop the depths too few other views agree with, then integrate 16 per launch ----
@@ -174,11 +194,15 @@ def run(args, state=None):
     ms["write"] = 1e3 * (time.perf_counter() - t0)
     if state is not None:
         state.update(model=model, volume=volume, vertices=v, triangles=t, colors=colors)
+        if cloud is not None:
+            state.update(cloud=cloud)
     rec = {"scan": args.scan, "views_fused": volume.n_views, "lattice": list(volume.shape), "voxel": voxel, "trunc": volume.trunc,
            "observed_share": volume.observed_share(), "vertices": int(len(v)), "triangles": int(len(t)), "depth": args.depth,
            "colors": bool(args.colors), "cleaned": bool(args.clean_mesh), "mesh": mesh_path, "ms": ms}
     if filtered is not None:
         rec.update(min_consistent=args.min_consistent, kept_share=sum(filtered["kept"]) / max(sum(filtered["measured"]), 1))
+    if cloud is not None:
+        rec.update(points=int(len(cloud.points)), points_file=points_path)
     if args.eval_dir is not None:
         t0 = time.perf_counter()
         d2s, s2d, overall = dtu_eval.evaluate_scan(mesh_path, args.eval_dir, args.scan, patch_size=args.patch_size,
@@ -186,6 +210,13 @@ def run(args, state=None):
                                                    rng=np.random.default_rng(args.shuffle_seed), device=args.eval_device)
         ms["evaluate"] = 1e3 * (time.perf_counter() - t0)
         rec.update(d2s=d2s, s2d=s2d, chamfer=overall)
+        if cloud is not None:
+            t0 = time.perf_counter()
+            d2s, s2d, overall = dtu_eval.evaluate_scan(points_path, args.eval_dir, args.scan, mode="pcd", patch_size=args.patch_size,
+                                                       max_dist=args.max_dist, downsample_density=args.downsample_density,
+                                                       rng=np.random.default_rng(args.shuffle_seed), device=args.eval_device)
+            ms["evaluate_points"] = 1e3 * (time.perf_counter() - t0)
+            rec.update(pcd_d2s=d2s, pcd_s2d=s2d, pcd_chamfer=overall)
     with open(os.path.join(args.out_dir, f"fused_scan{args.scan}.json"), "w") as f:
         json.dump(rec, f)
     return rec

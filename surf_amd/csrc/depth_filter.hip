@@ -12,7 +12,8 @@
 //    consecutive pixels of the flat index (best-coalesced reference streams, a long thin footprint in each source map);
 //    TW = 16 / 8: a wavefront covers a 16 x 4 / 8 x 8 tile of a 32 x 8 block tile (a compact footprint in each source map).
 //    The library is compiled with -ffp-contract=off; every line below is one fp32 operation per operator, in exactly this order
-//    (surf_amd/fusion.py consistency_host mirrors it in numpy fp32 and the tests demand equality).  With P = [M | t] per view,
+//    (surf_amd/fusion.py consistency_host mirrors it in numpy fp32 and the tests demand equality; the code is
+//    surf_consistency_rule in consistency_rule.h, which point_cloud.hip includes too).  With P = [M | t] per view,
 //    A_rs = M_s M_r^-1, b_rs = t_s - A_rs t_r (and A_sr, b_sr likewise), formed on the host in float64 and rounded once:
 //        d  = depth_r[y, x] * dscale_r;     the pixel is "measured" iff d > 0 and d <= FLT_MAX   (else nothing is done)
 //        q  = ((float)x * d, (float)y * d, d);      for each source s, in the order given:
@@ -31,23 +32,9 @@
 //        out  = 0 where not kept; depth_r[y, x] unchanged where kept, or with `average`
 //               ((zsum + d) / (float)(count + 1)) / dscale_r       (the mean over the reference and its agreeing sources)
 // Both are bandwidth / gather kernels: 256-thread blocks, no LDS.
-#include <float.h>
-#include <math.h>
-
-#include "common.h"
+#include "consistency_rule.h"        // the rule itself (surf_consistency_rule), shared with point_cloud.hip
 
 namespace {
-
-struct FilterSource {
-  float A_rs[9], b_rs[3], A_sr[9], b_sr[3];
-  const float* depth;
-  int H, W;
-  float dscale;
-  int pad;
-};
-struct FilterSources { FilterSource s[SURF_FUSE_MAX_VIEWS]; };
-
-__device__ __forceinline__ bool measured(float d) { return d > 0.0f && d <= FLT_MAX; }
 
 template <int TW>
 __global__ __launch_bounds__(256) void depth_consistency_kernel(const float* __restrict__ depth_r, int H, int W, float dscale_r,
@@ -69,40 +56,15 @@ __global__ __launch_bounds__(256) void depth_consistency_kernel(const float* __r
   }
   const int64_t i = (int64_t)y * W + x;
   const float d = depth_r[i] * dscale_r;
-  if (!measured(d)) return;
+  if (!surf_measured(d)) return;
   const float xf = (float)x, yf = (float)y;
   const float qx = xf * d, qy = yf * d, qz = d;
   int cnt = count[i];
   float zs = zsum[i];
   const int cnt0 = cnt;
   for (int s = 0; s < n_sources; ++s) {
-    const FilterSource& S = sources.s[s];
-    const float ux = ((S.A_rs[0] * qx + S.A_rs[1] * qy) + S.A_rs[2] * qz) + S.b_rs[0];
-    const float uy = ((S.A_rs[3] * qx + S.A_rs[4] * qy) + S.A_rs[5] * qz) + S.b_rs[1];
-    const float uz = ((S.A_rs[6] * qx + S.A_rs[7] * qy) + S.A_rs[8] * qz) + S.b_rs[2];
-    if (!(uz > 0.0f)) continue;
-    const float sx = ux / uz, sy = uy / uz;
-    if (!(sx >= 0.0f && sx <= (float)(S.W - 1) && sy >= 0.0f && sy <= (float)(S.H - 1))) continue;
-    const float x0f = floorf(sx), y0f = floorf(sy);
-    const float fx = sx - x0f, fy = sy - y0f;
-    const int x0 = (int)x0f, y0 = (int)y0f;                     // 0 <= x0 <= Ws-1, 0 <= y0 <= Hs-1 by the test above
-    const int x1 = min(x0 + 1, S.W - 1), y1 = min(y0 + 1, S.H - 1);
-    const int64_t r0 = (int64_t)y0 * S.W, r1 = (int64_t)y1 * S.W;
-    const float d00 = S.depth[r0 + x0] * S.dscale, d01 = S.depth[r0 + x1] * S.dscale;
-    const float d10 = S.depth[r1 + x0] * S.dscale, d11 = S.depth[r1 + x1] * S.dscale;
-    if (!(measured(d00) && measured(d01) && measured(d10) && measured(d11))) continue;
-    const float top = d00 + (d01 - d00) * fx;
-    const float bot = d10 + (d11 - d10) * fx;
-    const float ds = top + (bot - top) * fy;
-    const float vx = sx * ds, vy = sy * ds, vz = ds;
-    const float wx = ((S.A_sr[0] * vx + S.A_sr[1] * vy) + S.A_sr[2] * vz) + S.b_sr[0];
-    const float wy = ((S.A_sr[3] * vx + S.A_sr[4] * vy) + S.A_sr[5] * vz) + S.b_sr[1];
-    const float wz = ((S.A_sr[6] * vx + S.A_sr[7] * vy) + S.A_sr[8] * vz) + S.b_sr[2];
-    if (!(wz > 0.0f)) continue;
-    const float ex = wx / wz - xf, ey = wy / wz - yf;
-    const float e2 = ex * ex + ey * ey;
-    const float rel = fabsf(wz - d) / d;
-    if (!(e2 < px2 && rel < rel_thresh)) continue;
+    float wz, sx, sy;
+    if (!surf_consistency_rule(sources.s[s], xf, yf, d, qx, qy, qz, px2, rel_thresh, &wz, &sx, &sy)) continue;
     cnt += 1;
     zs = zs + wz;
   }
@@ -121,7 +83,7 @@ __global__ __launch_bounds__(256) void depth_consistency_finish_kernel(const flo
   const float raw = depth_r[i];
   const float d = raw * dscale_r;
   const int cnt = count[i];
-  const bool k = measured(d) && cnt >= min_consistent;
+  const bool k = surf_measured(d) && cnt >= min_consistent;
   float out = 0.0f;
   if (k) out = average ? ((zsum[i] + d) / (float)(cnt + 1)) / dscale_r : raw;
   out_depth[i] = out;
@@ -148,21 +110,8 @@ extern "C" int surf_depth_consistency(const float* depth_r, int H, int W, float 
   if (n_sources > SURF_FUSE_MAX_VIEWS) return SURF_E_LIMIT;
   if ((int64_t)H * W >= ((int64_t)1 << 31) || H > side_max || W > side_max || (H + 7) / 8 > 65535) return SURF_E_LIMIT;
   FilterSources sources;
-  for (int s = 0; s < n_sources; ++s) {
-    FilterSource& S = sources.s[s];
-    const int Hs = h_hw[2 * s], Ws = h_hw[2 * s + 1];
-    if (!h_depths[s] || Hs < 1 || Ws < 1) return SURF_E_ARG;
-    if ((int64_t)Hs * Ws >= ((int64_t)1 << 31) || Hs > side_max || Ws > side_max) return SURF_E_LIMIT;
-    const float* T = h_T + 24 * s;
-    for (int e = 0; e < 9; ++e) { S.A_rs[e] = T[e]; S.A_sr[e] = T[12 + e]; }
-    for (int e = 0; e < 3; ++e) { S.b_rs[e] = T[9 + e]; S.b_sr[e] = T[21 + e]; }
-    S.depth = h_depths[s];
-    S.H = Hs;
-    S.W = Ws;
-    S.dscale = h_dscale[s];
-    S.pad = 0;
-  }
-  for (int s = n_sources; s < SURF_FUSE_MAX_VIEWS; ++s) sources.s[s] = FilterSource{};
+  const int bad = surf_fill_filter_sources(sources, h_T, h_depths, h_hw, h_dscale, n_sources);
+  if (bad) return bad;
   if (tile_w == 64)
     launch_consistency<64>(depth_r, H, W, dscale_r, sources, n_sources, px2, rel_thresh, count, zsum, (hipStream_t)stream);
   else if (tile_w == 16)

@@ -17,6 +17,10 @@ Which pixels go in: filter_views(views, min_consistent) keeps the depths that en
 projected into another view, that view's depth is read there and projected back; it agrees when the round trip ends within a
 pixel of where it started and within 1 % of the depth (csrc/depth_filter.hip, 16 sources per launch; consistency_host is its
 numpy-fp32 mirror, equal arrays again).  It needs no object masks, unlike the DTU cleaner.
+
+The other product of the same depth maps: fuse_points(views, min_consistent) merges the consistent depths into ONE point cloud,
+one point per surface sample (csrc/point_cloud.hip; backend="host" is its numpy-fp32 mirror, equal arrays) - no lattice, no
+quantisation to a voxel size; mesh_io.write_ply_points writes it, evaluation.dtu_eval scores it with mode="pcd".
 """
 from collections import namedtuple
 
@@ -152,10 +156,11 @@ def pair_transforms(view_r, view_s):
     return _pair(_split_P(view_r), _split_P(view_s))
 
 
-def consistency_host(views, r, sources, px_thresh=CONSISTENCY_PX, rel_thresh=CONSISTENCY_REL):
+def consistency_host(views, r, sources, px_thresh=CONSISTENCY_PX, rel_thresh=CONSISTENCY_REL, matches=None):
     """The rule of depth_filter.hip's header comment in numpy fp32, one operation per operator in its order, over the whole map
     of views[r], source by source (pixels are independent, so this is the kernel's per-pixel loop).  sources: indices into
-    `views`, tested in this order.  Returns (count (H, W) int32, zsum (H, W) fp32)."""
+    `views`, tested in this order.  Returns (count (H, W) int32, zsum (H, W) fp32).  matches (list, optional): receives per
+    source (s, agree (H, W) bool, sx, sy (H, W) fp32), the pixel's projection into s (meaningful where it agrees)."""
     f32 = np.float32
     ref = views[r]
     depth_r = _np(ref.depth, f32)
@@ -203,6 +208,8 @@ def consistency_host(views, r, sources, px_thresh=CONSISTENCY_PX, rel_thresh=CON
             ok &= (e2 < px2) & (rel < rel_thresh)
             count += ok
             zsum[...] = np.where(ok, zsum + wz, zsum)
+            if matches is not None:
+                matches.append((s, ok, sx, sy))
     return count, zsum
 
 
@@ -292,6 +299,151 @@ def filter_views(views, min_consistent, px_thresh=CONSISTENCY_PX, rel_thresh=CON
         stats["kept"] = [int(t[1]) for t in tallies]
         stats["count_hist"] = [np.asarray(t[2:], dtype=np.int64) for t in tallies]
     return out
+
+
+# ---- fused point clouds: the consistent depths of all views merged into one cloud (csrc/point_cloud.hip) ----
+
+PointCloud = namedtuple("PointCloud", "points colors origin")
+PointCloud.__doc__ = """A fused cloud: points (N, 3) fp32 in the world frame, colors (N, 3) uint8 or None, origin (N, 2) int32 =
+(view index, flat row-major pixel index) of the pixel a point was lifted from; ordered by view, then pixel."""
+
+
+def lift_transform(view):
+    """The 12 fp32 values (M^-1 row-major, then c = -M^-1 t) of a view's P = [M | t]: X = M^-1 (x z, y z, z) + c.  Formed in
+    float64 and rounded once, so that no fp32 subtraction of the large t takes place."""
+    M, t, M_inv = _split_P(view)
+    return np.concatenate([M_inv.reshape(9), -(M_inv @ t)]).astype(np.float32)
+
+
+def lift_host(lift, x, y, z):
+    """The lift of point_cloud.hip's header comment in numpy fp32: pixels (x, y) (integer arrays) at depth z (fp32, world units)
+    -> points (n, 3) fp32."""
+    f32 = np.float32
+    lift, z = np.asarray(lift, f32), np.asarray(z, f32)
+    qx, qy = np.asarray(x).astype(f32) * z, np.asarray(y).astype(f32) * z
+    return np.stack([((lift[3 * k] * qx + lift[3 * k + 1] * qy) + lift[3 * k + 2] * z) + lift[9 + k] for k in range(3)], axis=-1)
+
+
+def quantise_colors_host(c):
+    """fp32 colours -> uint8 as fuse_vertex_colors_kernel converts: q = c * 256; q = fmin(fmax(q, 0), 255); (uint8)q."""
+    with np.errstate(all="ignore"):
+        q = np.asarray(c, np.float32) * np.float32(256.0)
+        return np.fmin(np.fmax(q, np.float32(0.0)), np.float32(255.0)).astype(np.uint8)
+
+
+def fuse_points(views, min_consistent, px_thresh=CONSISTENCY_PX, rel_thresh=CONSISTENCY_REL, sources=None, average=True,
+                backend="device", device=None, stats=None):
+    """The depth maps of `views` merged into one PointCloud with one point per surface sample (the rule is written out in
+    csrc/point_cloud.hip's header comment).  Views are visited in index order; a pixel that is measured, not yet used and that at
+    least min_consistent of its sources agree with (filter_views' test) is emitted, and the pixel it lands on in every agreeing
+    source is marked used: it may still support other views, but is not emitted again.  min_consistent = 0 emits every unused
+    measured pixel.  sources: None = every other view, or per view the list of the indices it is tested against
+    (nearest_sources), never itself.  average: a point is lifted at the mean depth over the view and its agreeing sources.
+    Colours are image[y, x] as uint8 when the views carry images (all of them or none).  backend "device"
+    (csrc/point_cloud.hip; the arrays are copied to the host once, at the end) or "host" (numpy fp32: equal arrays).
+    stats (dict, optional): receives per view "candidates" (measured, unused pixels), "emitted" (points) and "marked" (pixels of
+    other views it newly marked used), and "used": the final used maps, (H, W) uint8 arrays."""
+    if backend not in ("device", "host"):
+        raise ValueError(f"fuse_points: backend {backend!r} (device or host)")
+    if int(min_consistent) != min_consistent or min_consistent < 0:
+        raise ValueError("fuse_points: min_consistent is a count >= 0")
+    views = [v if isinstance(v, DepthView) else DepthView(*v) for v in views]
+    n = len(views)
+    if sources is None:
+        sources = [[s for s in range(n) if s != r] for r in range(n)]
+    if len(sources) != n:
+        raise ValueError("fuse_points: sources lists the source views of every view")
+    for r, src in enumerate(sources):
+        if any(int(s) != s or not 0 <= s < n or s == r for s in src):
+            raise ValueError(f"fuse_points: sources[{r}] holds indices of other views")
+    with_colors = n > 0 and views[0].image is not None
+    if any((v.image is not None) != with_colors for v in views):
+        raise ValueError("fuse_points: either every view carries an image or none does")
+    for r, v in enumerate(views):
+        if len(v.depth.shape) != 2 or (with_colors and tuple(v.image.shape) != tuple(v.depth.shape) + (3,)):
+            raise ValueError(f"fuse_points: views[{r}] holds depth (H, W) and image (H, W, 3)")
+    min_consistent, average = int(min_consistent), bool(average)
+    lifts = [lift_transform(v) for v in views]
+    points, colors, origin, tallies = [], [], [], []
+    if backend == "device":
+        if not torch.cuda.is_available():
+            raise RuntimeError("fuse_points(backend='device') needs a GPU (the SuRF hot path has no CPU fallback)")
+        dev = torch.device("cuda" if device is None else device)
+
+        def up(x):
+            return x.to(dev, torch.float32).contiguous() if torch.is_tensor(x) else \
+                torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
+        depths = [up(v.depth) for v in views]
+        used = [torch.zeros(d.shape, dtype=torch.uint8, device=dev) for d in depths]
+        split = [_split_P(v) for v in views]
+        for r, view in enumerate(views):
+            cand = ops.points_candidates(depths[r], used[r])
+            ref = (cand, float(view.dscale))
+            count = torch.zeros(cand.shape, dtype=torch.int32, device=dev)
+            zsum = torch.zeros(cand.shape, dtype=torch.float32, device=dev)
+            chunks = [[(_pair(split[r], split[s]), depths[s], float(views[s].dscale)) for s in sources[r][c:c + ops.FUSE_MAX_VIEWS]]
+                      for c in range(0, len(sources[r]), ops.FUSE_MAX_VIEWS)]
+            for chunk in chunks:
+                ops.depth_consistency(ref, chunk, count, zsum, px_thresh, rel_thresh)
+            keep = ops.depth_consistency_finish(ref, count, zsum, min_consistent)[1]
+            if stats is not None:
+                targets = sorted(set(sources[r]))
+                before = sum(used[s].sum() for s in targets) if targets else torch.zeros((), dtype=torch.int64, device=dev)
+            for c, chunk in enumerate(chunks):
+                ops.points_mark(ref, keep, chunk, [used[s] for s in sources[r][c * ops.FUSE_MAX_VIEWS:(c + 1) * ops.FUSE_MAX_VIEWS]],
+                                px_thresh, rel_thresh)
+            kept = torch.nonzero(keep.reshape(-1)).reshape(-1)                    # ascending: the cloud's order within a view
+            p, c, o = ops.points_lift(ref, count, zsum, kept, lifts[r], r, average, up(view.image) if with_colors else None)
+            points.append(p)
+            colors.append(c)
+            origin.append(o)
+            if stats is not None:
+                after = sum(used[s].sum() for s in targets) if targets else before
+                n_cand = ops.depth_consistency_finish(ref, count, zsum, 0)[1].sum()
+                tallies.append(torch.stack([n_cand, after - before]))
+        if n:
+            points, origin = torch.cat(points).cpu().numpy(), torch.cat(origin).cpu().numpy()
+            colors = torch.cat(colors).cpu().numpy() if with_colors else None
+        if stats is not None:
+            tallies = [t.cpu().numpy() for t in tallies]
+            stats["used"] = [u.cpu().numpy() for u in used]
+    else:
+        f32 = np.float32
+        host = [view._replace(depth=_np(view.depth, f32)) for view in views]
+        used = [np.zeros(v.depth.shape, np.uint8) for v in host]
+        for r, view in enumerate(host):
+            cand = view._replace(depth=np.where(used[r] != 0, f32(0.0), view.depth))
+            masked = host[:r] + [cand] + host[r + 1:]                            # only the reference is masked: sources are read as they are
+            matches = []
+            count, zsum = consistency_host(masked, r, sources[r], px_thresh, rel_thresh, matches)
+            keep = finish_host(cand, count, zsum, min_consistent)[1]
+            before = sum(int(u.sum()) for u in used)
+            for s, agree, sx, sy in matches:
+                hit = keep & agree
+                used[s][np.rint(sy[hit]).astype(np.int64), np.rint(sx[hit]).astype(np.int64)] = 1
+            H, W = cand.depth.shape
+            kept = np.flatnonzero(keep)
+            y, x = kept // W, kept % W
+            with np.errstate(all="ignore"):
+                d = cand.depth * f32(view.dscale)
+                z = ((zsum + d) / (count + 1).astype(f32) if average else d).astype(f32)
+            points.append(lift_host(lifts[r], x, y, z[y, x]))
+            if with_colors:
+                colors.append(quantise_colors_host(_np(view.image, f32)[y, x]))
+            origin.append(np.stack([np.full(len(kept), r), kept], axis=-1).astype(np.int32))
+            tallies.append((int(finish_host(cand, count, zsum, 0)[1].sum()), sum(int(u.sum()) for u in used) - before))
+        if n:
+            points, origin = np.concatenate(points).astype(f32), np.concatenate(origin)
+            colors = np.concatenate(colors) if with_colors else None
+        if stats is not None:
+            stats["used"] = used
+    if not n:
+        points, colors, origin = np.zeros((0, 3), np.float32), None, np.zeros((0, 2), np.int32)
+    if stats is not None:
+        stats["candidates"] = [int(t[0]) for t in tallies]
+        stats["marked"] = [int(t[1]) for t in tallies]
+        stats["emitted"] = [int(c) for c in np.bincount(origin[:, 0], minlength=n)]
+    return PointCloud(points, colors, origin)
 
 
 class FusionVolume:

@@ -1928,6 +1928,30 @@ def _chk_consistency_state(depth, count, zsum, what):
         raise ValueError(f"{what}: ref depth, count and zsum on one device")
 
 
+def _consistency_sources(sources, depth_r, what):
+    """The host arrays of a launch's source table: (T (n, 24) fp32, hw (n, 2) int32, dscale (n) fp32, the depth tensors)."""
+    n = len(sources)
+    T = np.empty((n, 24), dtype=np.float32)
+    hw = np.empty((n, 2), dtype=np.int32)
+    dscale = np.empty(n, dtype=np.float32)
+    depths = []
+    for s, (Ts, depth, ds) in enumerate(sources):
+        _chk(depth, torch.float32, f"sources[{s}].depth")
+        if depth.dim() != 2 or depth.numel() == 0:
+            raise ValueError(f"{what}: sources[{s}].depth (Hs, Ws)")
+        if depth.device != depth_r.device:
+            raise ValueError(f"{what}: sources[{s}].depth is not on the reference's device")
+        Ts = np.concatenate([np.asarray(p, dtype=np.float32).reshape(-1) for p in Ts]) if isinstance(Ts, (tuple, list)) else \
+            np.asarray(Ts, dtype=np.float32).reshape(-1)
+        if Ts.shape != (24,):
+            raise ValueError(f"{what}: sources[{s}] transforms hold {Ts.size} values, not A_rs, b_rs, A_sr, b_sr = 24")
+        T[s] = Ts
+        hw[s] = depth.shape
+        dscale[s] = ds
+        depths.append(depth)
+    return T, hw, dscale, depths
+
+
 def depth_consistency(ref, sources, count, zsum, px_thresh=1.0, rel_thresh=0.01, tile_w=None):
     """One launch of surf_depth_consistency: the reference map ref = (depth (H, W) fp32 device tensor, dscale) is tested against
     `sources`, at most FUSE_MAX_VIEWS of them, in order; count (H, W) int32 and zsum (H, W) fp32 are updated in place (a further
@@ -1940,24 +1964,7 @@ def depth_consistency(ref, sources, count, zsum, px_thresh=1.0, rel_thresh=0.01,
     n = len(sources)
     if n == 0:
         return
-    T = np.empty((n, 24), dtype=np.float32)
-    hw = np.empty((n, 2), dtype=np.int32)
-    dscale = np.empty(n, dtype=np.float32)
-    depths = []
-    for s, (Ts, depth, ds) in enumerate(sources):
-        _chk(depth, torch.float32, f"sources[{s}].depth")
-        if depth.dim() != 2 or depth.numel() == 0:
-            raise ValueError(f"depth_consistency: sources[{s}].depth (Hs, Ws)")
-        if depth.device != depth_r.device:
-            raise ValueError(f"depth_consistency: sources[{s}].depth is not on the reference's device")
-        Ts = np.concatenate([np.asarray(p, dtype=np.float32).reshape(-1) for p in Ts]) if isinstance(Ts, (tuple, list)) else \
-            np.asarray(Ts, dtype=np.float32).reshape(-1)
-        if Ts.shape != (24,):
-            raise ValueError(f"depth_consistency: sources[{s}] transforms hold {Ts.size} values, not A_rs, b_rs, A_sr, b_sr = 24")
-        T[s] = Ts
-        hw[s] = depth.shape
-        dscale[s] = ds
-        depths.append(depth)
+    T, hw, dscale, depths = _consistency_sources(sources, depth_r, "depth_consistency")
     px = np.float32(px_thresh)
     H, W = (int(v) for v in depth_r.shape)
     _lib.lib().surf_depth_consistency(_p(depth_r), H, W, ctypes.c_float(float(dscale_r)), _np_ptr(T), _ptr_array(depths),
@@ -1980,6 +1987,78 @@ def depth_consistency_finish(ref, count, zsum, min_consistent, average=False):
         _lib.lib().surf_depth_consistency_finish(_p(depth_r), ctypes.c_float(float(dscale_r)), _p(count), _p(zsum), depth_r.numel(),
                                                  int(min_consistent), int(bool(average)), _p(out), _p(keep), _stream())
     return out, keep
+
+
+# ------------------------------------------------------------------------------------------------
+# fused point clouds (point_cloud.hip): consistent depths of many views merged into one cloud (surf_amd/fusion.py fuse_points)
+# ------------------------------------------------------------------------------------------------
+
+
+def points_candidates(depth, used):
+    """surf_points_candidates: the depth map (H, W) fp32 with the pixels of used (H, W) uint8 != 0 set to 0 (no measurement)."""
+    _chk(depth, torch.float32, "points_candidates: depth")
+    _chk(used, torch.uint8, "points_candidates: used")
+    if depth.dim() != 2 or used.shape != depth.shape or used.device != depth.device:
+        raise ValueError("points_candidates: depth and used (H, W) on one device")
+    out = torch.empty_like(depth)
+    if depth.numel():
+        _lib.lib().surf_points_candidates(_p(depth), _p(used), depth.numel(), _p(out), _stream())
+    return out
+
+
+def points_mark(ref, keep, sources, used, px_thresh=1.0, rel_thresh=0.01):
+    """One launch of surf_points_mark: at the pixels of the reference map ref = (candidate depth (H, W) fp32, dscale) with
+    keep (H, W) uint8 != 0 the consistency rule is re-run against `sources` (as for depth_consistency, at most FUSE_MAX_VIEWS)
+    and used[s] (Hs, Ws) uint8, the used map of sources[s], gets a 1 at the pixel each agreeing source was matched at."""
+    depth_r, dscale_r = ref
+    _chk(depth_r, torch.float32, "points_mark: ref depth")
+    _chk(keep, torch.uint8, "points_mark: keep")
+    if depth_r.dim() != 2 or keep.shape != depth_r.shape or keep.device != depth_r.device:
+        raise ValueError("points_mark: ref depth and keep (H, W) on one device")
+    n = len(sources)
+    if len(used) != n:
+        raise ValueError("points_mark: one used map per source")
+    if n == 0 or depth_r.numel() == 0:
+        return
+    T, hw, dscale, depths = _consistency_sources(sources, depth_r, "points_mark")
+    for s, (u, depth) in enumerate(zip(used, depths)):
+        _chk(u, torch.uint8, f"points_mark: used[{s}]")
+        if u.shape != depth.shape or u.device != depth.device:
+            raise ValueError(f"points_mark: used[{s}] has the shape and device of sources[{s}].depth")
+    px = np.float32(px_thresh)
+    H, W = (int(v) for v in depth_r.shape)
+    _lib.lib().surf_points_mark(_p(depth_r), H, W, ctypes.c_float(float(dscale_r)), _p(keep), _np_ptr(T), _ptr_array(depths),
+                                _ptr_array(used), _np_ptr(hw), _np_ptr(dscale), n, ctypes.c_float(float(px * px)),
+                                ctypes.c_float(float(np.float32(rel_thresh))), _stream())
+
+
+def points_lift(ref, count, zsum, kept, lift, view, average=True, image=None):
+    """surf_points_lift: (points (n, 3) fp32, colors (n, 3) uint8 or None, origin (n, 2) int32) of the kept pixels of the
+    reference map ref = (candidate depth (H, W) fp32, dscale).  kept (n,) int64: their flat indices, ascending; count / zsum:
+    depth_consistency's state; lift: the 12 fp32 values M^-1 (row-major) and -M^-1 t of the view's P = [M | t] on the host;
+    view: the index written to origin[:, 0]; image (H, W, 3) fp32 or None.  The fp32 operation order is written out in
+    point_cloud.hip's header comment."""
+    depth_r, dscale_r = ref
+    _chk_consistency_state(depth_r, count, zsum, "points_lift")
+    _chk(kept, torch.int64, "points_lift: kept")
+    if kept.dim() != 1 or kept.device != depth_r.device:
+        raise ValueError("points_lift: kept (n,) on the reference's device")
+    lift = np.ascontiguousarray(np.asarray(lift, dtype=np.float32).reshape(-1))
+    if lift.shape != (12,):
+        raise ValueError("points_lift: lift holds M^-1 and -M^-1 t = 12 values")
+    if image is not None:
+        _chk(image, torch.float32, "points_lift: image")
+        if tuple(image.shape) != tuple(depth_r.shape) + (3,) or image.device != depth_r.device:
+            raise ValueError("points_lift: image (H, W, 3) on the reference's device")
+    n, dev = int(kept.shape[0]), depth_r.device
+    points = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    colors = None if image is None else torch.empty(n, 3, dtype=torch.uint8, device=dev)
+    origin = torch.empty(n, 2, dtype=torch.int32, device=dev)
+    if n:
+        H, W = (int(v) for v in depth_r.shape)
+        _lib.lib().surf_points_lift(_p(depth_r), H, W, ctypes.c_float(float(dscale_r)), _p(count), _p(zsum), int(bool(average)),
+                                    _p(kept), n, _np_ptr(lift), _p(image), int(view), _p(points), _p(colors), _p(origin), _stream())
+    return points, colors, origin
 
 
 # ------------------------------------------------------------------------------------------------
