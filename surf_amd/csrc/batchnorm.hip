@@ -5,6 +5,9 @@
 //   surf_bn_relu_apply:   out = relu(x scale + shift) (+ skip)
 // Statistics are reduced deterministically in fp64: per-workgroup partials, then a serial finalise (as the FPN's
 // InstanceNorm, fpn.hip).  Byte-bound: x is read twice, written once.
+// The sums are taken of x - pivot, pivot = the channel's value in row 0 (exact in fp64): var = E[(x - p)^2] - E[x - p]^2 then
+// cancels at the scale of the spread, not of the mean.  (Summing x itself lost the variance of a channel whose mean is 10^5 x its
+// spread: 1/sqrt(var + eps) off by 60 ulp at mean 15,600, var 0.003 - tests/test_sparse_unet_kernels.py.)
 #include "common.h"
 
 namespace {
@@ -17,17 +20,18 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict
   __shared__ double sh[2][256];
   const int c = threadIdx.x % C, g = threadIdx.x / C;
   double s1 = 0.0, s2 = 0.0, t1 = 0.0, t2 = 0.0;            // two independent fp64 chains per thread
+  const double piv = (double)x[c];                          // row 0 (file comment)
   const int64_t step = (int64_t)gridDim.x * G;
   int64_t r = (int64_t)blockIdx.x * G + g;
   for (; r + step < n; r += 2 * step) {
-    const double v = (double)x[r * C + c], w = (double)x[(r + step) * C + c];
+    const double v = (double)x[r * C + c] - piv, w = (double)x[(r + step) * C + c] - piv;
     s1 += v;
     s2 = fma(v, v, s2);
     t1 += w;
     t2 = fma(w, w, t2);
   }
   if (r < n) {
-    const double v = (double)x[r * C + c];
+    const double v = (double)x[r * C + c] - piv;
     s1 += v;
     s2 = fma(v, v, s2);
   }
@@ -68,15 +72,16 @@ __device__ __forceinline__ bool reduce_partials_channel(const double* __restrict
   return threadIdx.x == 0;
 }
 
-__global__ __launch_bounds__(256) void bn_finalize_kernel(const double* __restrict__ part, int blocks, int C, int64_t n, const float* __restrict__ gamma,
+__global__ __launch_bounds__(256) void bn_finalize_kernel(const double* __restrict__ part, int blocks, int C, int64_t n, const float* __restrict__ x, const float* __restrict__ gamma,
                                    const float* __restrict__ beta, float eps, float momentum, float* __restrict__ running_mean,
                                    float* __restrict__ running_var, float* __restrict__ scale, float* __restrict__ shift,
                                    float* __restrict__ batch_stats) {
   double s1, s2;
   const int c = blockIdx.x;
   if (!reduce_partials_channel(part, blocks, C, c, s1, s2)) return;
-  const double mean = s1 / (double)n;
-  double var = s2 / (double)n - mean * mean;      // biased (what the normalisation uses)
+  const double dm = s1 / (double)n;                // the sums are of x - pivot (bn_partial_kernel)
+  const double mean = (double)x[c] + dm;
+  double var = s2 / (double)n - dm * dm;          // biased (what the normalisation uses)
   if (var < 0.0) var = 0.0;
   const float sc = gamma[c] / sqrtf((float)var + eps);
   scale[c] = sc;
@@ -316,7 +321,7 @@ extern "C" int surf_bn_train_affine(const float* x, int64_t n, int channels, con
     case 64: hipLaunchKernelGGL(bn_partial_kernel<64>, dim3(blocks), dim3(256), 0, s, x, n, part); break;
     default: return SURF_E_LIMIT;
   }
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3(channels), dim3(256), 0, s, part, blocks, channels, n, gamma, beta, eps, momentum,
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3(channels), dim3(256), 0, s, part, blocks, channels, n, x, gamma, beta, eps, momentum,
                      running_mean, running_var, scale, shift, batch_stats);
   return surf_check_launch();
 }
