@@ -525,7 +525,7 @@ int surf_costvol_backward(const int32_t* coords, const float* g, int64_t n, int 
  * big (N, Hs S, Ws S, cb), small (N, Hs, Ws, cs).  Conv2d: big = layer input, small = d output -> [ky][kx][ci][co];
  * ConvTranspose2d (S = 2): big = d output, small = layer input -> [ky][kx][co][ci].  Input gradients run on the forward
  * kernels: stride 1 -> surf_conv3x3 with the flipped, transposed kernel; stride 2 -> surf_deconv3x3_s2; deconv -> stride-2
- * surf_conv3x3.  InstanceNorm + ReLU backward = surf_bn_relu_backward per view (scale = rstd, shift = -mean rstd). */
+ * surf_conv3x3.  InstanceNorm + ReLU backward = surf_inorm_relu_backward, one call for all views. */
 int64_t surf_conv3x3_wgrad_workspace_floats(int N, int Hs, int Ws, int cb, int cs);
 int surf_conv3x3_wgrad(const float* big, const float* small, int N, int Hs, int Ws, int cb, int cs, int stride,
                        float* workspace, float* out, void* stream);

@@ -9,6 +9,9 @@
 // C_in >= 16 (forward, input gradient, weight gradient) run on the matrix cores, fpn_mfma.hip; the entry points below dispatch
 // (SURF_FPN_VALU=1 in the environment keeps everything on the kernels of this file: the A/B switch of the tests).
 // InstanceNorm statistics are reduced deterministically in fp64 (per-block partials, then a serial finalise).
+// The sums are taken of x - pivot, pivot = the channel's value at pixel 0 of the image (exact in fp64): var = E[(x - p)^2] -
+// E[x - p]^2 then cancels at the scale of the spread, not of the mean.  (Summing x itself put rstd off by 36 float32 ulp at mean
+// 19,200 / spread 1 and by 411 ulp at mean 15,600 / spread 0.055 - tests/test_fpn_kernels.py.)
 #include "common.h"
 
 namespace {
@@ -109,17 +112,18 @@ __global__ __launch_bounds__(256) void inorm_partial_kernel(const float* __restr
   // four independent accumulator pairs: the fp64 add / fma chains are what a thread waits for, not the loads
   double sa[4] = {0.0, 0.0, 0.0, 0.0}, sb[4] = {0.0, 0.0, 0.0, 0.0};
   const float* __restrict__ xn = x + (int64_t)n * HW * C;
+  const double piv = (double)xn[c];                                      // pixel 0 (file comment)
   int p = p0 + g;
   for (; p + 3 * G < p1; p += 4 * G) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      const double v = (double)xn[(int64_t)(p + u * G) * C + c];
+      const double v = (double)xn[(int64_t)(p + u * G) * C + c] - piv;
       sa[u] += v;
       sb[u] = fma(v, v, sb[u]);
     }
   }
   for (; p < p1; p += G) {
-    const double v = (double)xn[(int64_t)p * C + c];
+    const double v = (double)xn[(int64_t)p * C + c] - piv;
     sa[0] += v;
     sb[0] = fma(v, v, sb[0]);
   }
@@ -135,8 +139,9 @@ __global__ __launch_bounds__(256) void inorm_partial_kernel(const float* __restr
 }
 
 // one wavefront per (n, c): lanes stride over the partial blocks, wave sum in a fixed order (deterministic)
-__global__ __launch_bounds__(64) void inorm_finalize_kernel(const double* __restrict__ part, int N, int nblk, int C, int HW,
-                                                            float* __restrict__ stats /* (N, C, 2): mean, rstd */) {
+// (x is read at pixel 0 only, and before inorm_relu_kernel overwrites it in the in-place form: same stream)
+__global__ __launch_bounds__(64) void inorm_finalize_kernel(const double* __restrict__ part, const float* x, int N, int nblk, int C,
+                                                            int HW, float* __restrict__ stats /* (N, C, 2): mean, rstd */) {
   const int t = blockIdx.x;
   if (t >= N * C) return;
   const int n = t / C, c = t % C;
@@ -151,10 +156,10 @@ __global__ __launch_bounds__(64) void inorm_finalize_kernel(const double* __rest
     s2 += __shfl_xor(s2, o);
   }
   if (threadIdx.x != 0) return;
-  const double mean = s / HW;
-  double var = s2 / HW - mean * mean;
+  const double dm = s / HW;                                               // the sums are of x - pivot (inorm_partial_kernel)
+  double var = s2 / HW - dm * dm;
   if (var < 0.0) var = 0.0;
-  stats[t * 2 + 0] = (float)mean;
+  stats[t * 2 + 0] = (float)((double)x[(int64_t)n * HW * C + c] + dm);
   stats[t * 2 + 1] = (float)(1.0 / sqrt(var + 1e-5));
 }
 
@@ -367,7 +372,7 @@ extern "C" int surf_inorm_relu_out(const float* x, int N, int H, int W, int C, c
   const int HW = H * W;
   const int nblk = (HW + ST_PIX - 1) / ST_PIX;
   hipLaunchKernelGGL(inorm_partial_kernel, dim3(nblk, N), dim3(256), 0, st, x, HW, C, nblk, workspace);
-  hipLaunchKernelGGL(inorm_finalize_kernel, dim3(N * C), dim3(64), 0, st, workspace, N, nblk, C, HW, stats);
+  hipLaunchKernelGGL(inorm_finalize_kernel, dim3(N * C), dim3(64), 0, st, workspace, x, N, nblk, C, HW, stats);
   hipLaunchKernelGGL(inorm_relu_kernel, grid1d((int64_t)N * HW * (C / 4), 256), dim3(256), 0, st, x, out, stats, skip, N, HW, C);
   return surf_check_launch();
 }

@@ -119,7 +119,7 @@ class FeatureNetwork(nn.Module):
         """Reverse sweep: g_outs_c2f = gradients of the four texel4 outputs (coarse -> fine, like forward's return value).
         ACCUMULATES into the `.grad` of every convolution weight (or into `sink`, a grads.GradSink).  Input gradients reuse the forward kernels (stride 1: the
         flipped, transposed kernel; stride 2 <-> transposed convolution), weight gradients `surf_conv3x3_wgrad`, the
-        InstanceNorm + ReLU (+ skip) backward `surf_bn_relu_backward` per view."""
+        InstanceNorm + ReLU (+ skip) backward `surf_inorm_relu_backward`, one call for all views."""
         def acc(p, g):
             accumulate(p, g, sink)
 
