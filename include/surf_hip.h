@@ -910,6 +910,38 @@ int surf_fuse_vertex_colors(const double* vertices, int64_t n_vertices, const fl
                             void* stream);
 
 /*
+ * Brick-sparse depth-map fusion (surf_amd/fusion.py FusionVolume(sparse=True); fuse_sparse.hip): the state of surf_fuse_* kept only
+ * in the 8^3-point bricks that can carry a triangle, so that lattices of 2^31 points and more can be fused and meshed.  Added under
+ * SURF_ABI_VERSION 41 without a bump, like the entry points above.  The lattice (nx,ny,nz) is embedded in the cube of side
+ * res = max(nx,ny,nz) (2 <= res, res <= SURF_BAND_MAX_RES: SURF_E_LIMIT beyond) and uses the band layout above: table
+ * (surf_band_table_size(res) int32, -1 = not allocated), bricks (slot -> id, ascending ids), state tsdf / weight (n_slots * 512)
+ * and color (n_slots * 512, 3) fp32, brick-major.  The axes must be strictly increasing.  n_slots * 512 >= 2^31 is SURF_E_LIMIT.
+ * Call sequence:
+ *   surf_fuse_mark_bricks      once per view, ALL views before the first integration: mark[id] = 1 for every brick that can hold a
+ *                              point the view updates with less than the truncation distance, or a lattice neighbour of one.
+ *                              HOST h_lift (12) fp32 = M^-1 (row-major) then -M^-1 t of the view's P = [M | t], formed in float64
+ *                              and rounded once.  The rule and its fp32 operation order: fuse_sparse.hip's header comment.
+ *   surf_compact(mark) -> ids; surf_band_assign(ids, m, 0, table, bricks, mark)
+ *   surf_fuse_integrate_bricks surf_fuse_integrate over every point of the listed bricks, the same per-point arithmetic: the state
+ *                              equals the dense lattice's there, bit for bit.  Points past the upper faces are never updated.
+ *   surf_fuse_lattice          on the flat state -> vals (u = -tsdf where weight > 0, NaN elsewhere)
+ *   surf_band_classify_observed  surf_mc_classify_observed's flags for every band point, values read through the table (a missing
+ *                              brick reads NaN); then surf_compact / surf_band_keys / sort / surf_band_rank / surf_mc_count /
+ *                              surf_band_emit with res as above.  For an isovalue in (-1, 1) the mesh is the dense one, array for array.
+ *   surf_fuse_vertex_colors_bricks  surf_fuse_vertex_colors with the colour reads going through the table.
+ */
+int surf_fuse_mark_bricks(const float* depth, int H, int W, float dscale, const float* h_lift, const float* ax, const float* ay,
+                          const float* az, int nx, int ny, int nz, float trunc, uint8_t* mark, void* stream);
+int surf_fuse_integrate_bricks(float* tsdf, float* weight, float* color, const int32_t* bricks, int64_t n_slots, const float* ax,
+                               const float* ay, const float* az, int nx, int ny, int nz, const float* h_P,
+                               const float* const* h_depths, const float* const* h_images, const int* h_hw, const float* h_dscale,
+                               int n_views, float trunc, void* stream);
+int surf_band_classify_observed(const float* vals, const int32_t* table, const int32_t* bricks, int64_t n_slots, int nx, int ny,
+                                int nz, double isovalue, uint8_t* flags, void* stream);
+int surf_fuse_vertex_colors_bricks(const double* vertices, int64_t n_vertices, const float* color, const int32_t* table, int nx,
+                                   int ny, int nz, uint8_t* out, void* stream);
+
+/*
  * Multi-view geometric consistency of depth maps (surf_amd/fusion.py filter_views; depth_filter.hip): which pixels of a reference
  * depth map do enough other views agree with?  A pixel is lifted with its depth, projected into a source view, the source's depth
  * is read there (bilinear over four MEASURED taps), the source point is projected back, and the source agrees when the round trip

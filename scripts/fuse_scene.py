@@ -19,6 +19,9 @@ the evaluator's point-cloud mode when --eval_dir is given; the mesh and its fiel
 
 The lattice covers the union of the groups' normalised [-1, 1]^3 boxes (fusion.bounds_from_scale_mats; a first pass over the items
 reads their scale_mats) at --voxel_mm world units per step, or --resolution points along the longest side.
+With --sparse the lattice is brick-sparse (fusion.FusionVolume(sparse=True), csrc/fuse_sparse.hip): the same mesh from state kept
+only near the measured surfaces, for lattices of 2^31 points and more (a dense lattice of that size exits at once); the record
+gains `sparse`, `bricks`, `allocated_share` and `state_bytes`, and ms.finalize (allocation + integration of the recorded views).
 Measurement harness like scripts/dtu_chamfer.py: one scan per call, no logging framework, no resume logic."""
 import argparse
 import json
@@ -43,6 +46,10 @@ def parse_args(argv=None):
     size.add_argument("--voxel_mm", type=float, default=None, help="lattice step in world units (DTU: millimetres)")
     size.add_argument("--resolution", type=int, default=None, help="lattice points along the longest side of the box (default 256)")
     ap.add_argument("--trunc_voxels", type=float, default=4.0, help="truncation distance in lattice steps")
+    ap.add_argument("--sparse", action="store_true",
+                    help="brick-sparse lattice (fusion.FusionVolume(sparse=True), csrc/fuse_sparse.hip): state only near the measured "
+                         "surfaces, the same mesh; needed from 2^31 lattice points on.  The views' depth maps (and images) stay on "
+                         "the device until the mesh is taken")
     ap.add_argument("--depth", default="sdf_depth", choices=["sdf_depth", "render_depth"], help="which rendered depth map is fused")
     ap.add_argument("--colors", action="store_true", help="also fuse color_fine and write red green blue into the PLY")
     ap.add_argument("--min_consistent", type=int, default=0,
@@ -116,7 +123,11 @@ def run(args, state=None):
     t0 = time.perf_counter()
     lo, hi = fusion.bounds_from_scale_mats([dataset[i]["scale_mat"] for i in range(len(dataset))])
     voxel = args.voxel_mm if args.voxel_mm is not None else float((hi - lo).max()) / ((args.resolution or 256) - 1)
-    volume = fusion.FusionVolume((lo, hi, voxel), trunc=args.trunc_voxels * voxel, colors=args.colors, device=dev)
+    shape = [len(a) for a in fusion.lattice_axes(lo, hi, voxel)]
+    if not args.sparse and int(np.prod(shape, dtype=np.int64)) >= 2 ** 31:
+        raise SystemExit(f"fuse_scene: a dense lattice of {shape[0]} x {shape[1]} x {shape[2]} points is past the mesh step's limit "
+                         "of 2^31 points (and takes 8 to 20 B per point): use --sparse")
+    volume = fusion.FusionVolume((lo, hi, voxel), trunc=args.trunc_voxels * voxel, colors=args.colors, device=dev, sparse=args.sparse)
     ms["lattice"] = 1e3 * (time.perf_counter() - t0)
 
     def sync():
@@ -176,6 +187,12 @@ def run(args, state=None):
     if pending:
         flush()
 
+    if args.sparse:
+        # ---- integrate() only recorded the views: allocate bricks over all of them, then integrate all of them ----
+        t0 = time.perf_counter()
+        volume.finalize()
+        sync()
+        ms["finalize"] = 1e3 * (time.perf_counter() - t0)
     t0 = time.perf_counter()
     mesh = volume.extract_mesh()
     v, t, colors = mesh[0], mesh[1], (mesh[2] if args.colors else None)
@@ -199,6 +216,8 @@ def run(args, state=None):
     rec = {"scan": args.scan, "views_fused": volume.n_views, "lattice": list(volume.shape), "voxel": voxel, "trunc": volume.trunc,
            "observed_share": volume.observed_share(), "vertices": int(len(v)), "triangles": int(len(t)), "depth": args.depth,
            "colors": bool(args.colors), "cleaned": bool(args.clean_mesh), "mesh": mesh_path, "ms": ms}
+    if args.sparse:                                     # without the flag the record is what it was
+        rec.update(sparse=True, bricks=volume.n_bricks, allocated_share=volume.allocated_share(), state_bytes=volume.state_bytes())
     if filtered is not None:
         rec.update(min_consistent=args.min_consistent, kept_share=sum(filtered["kept"]) / max(sum(filtered["measured"]), 1))
     if cloud is not None:

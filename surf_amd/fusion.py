@@ -13,6 +13,14 @@ backend="device": csrc/fuse.hip (16 views per launch, the lattice point's state 
 cubes of csrc/mcubes.hip with the observed-corner rule.  backend="host": the numpy-fp32 mirror of the update sequence written
 out in fuse.hip's header comment, operation by operation - the two give equal arrays.  The mesh step always runs on the GPU.
 
+FusionVolume(..., sparse=True) (SparseFusionVolume, csrc/fuse_sparse.hip) keeps that state only in the 8^3-point bricks near the
+measured surfaces and returns the same mesh, array for array, for -1 < isovalue < 1 - also on lattices of 2^31 points and more,
+where the dense volume's mesh step stops (8 B per point, 20 B with colours, besides).  Only points some view updates with
+diff < trunc ever leave tsdf == 1, so only those and their lattice neighbours can carry geometry; bricks are allocated per depth
+pixel as a superset of the bricks that hold them, and every view is integrated over every allocated point with the dense
+arithmetic.  Allocation has to see all views first: integrate() records the views (device copies of depth and image: 33 MB per
+1080p view with colours) and the state is built at first use; a later integrate() rebuilds it.  The class docstring has the limits.
+
 Which pixels go in: filter_views(views, min_consistent) keeps the depths that enough other views agree with - a pixel is lifted,
 projected into another view, that view's depth is read there and projected back; it agrees when the round trip ends within a
 pixel of where it started and within 1 % of the depth (csrc/depth_filter.hip, 16 sources per launch; consistency_host is its
@@ -93,13 +101,14 @@ def lattice_axes(lo, hi, voxel):
     return [(lo[a] + voxel * np.arange(int(np.ceil((hi[a] - lo[a]) / voxel - 1e-9)) + 1)).astype(np.float32) for a in range(3)]
 
 
-def integrate_host(tsdf, weight, color, axes, views, trunc, stats=None):
+def integrate_host(tsdf, weight, color, axes, views, trunc, stats=None, points=None, valid=None):
     """The update sequence of fuse.hip's header comment in numpy fp32, one operation per operator in its order, over the whole
     lattice view by view (lattice points are independent, so this is the kernel's per-point loop).  tsdf / weight / color:
     fp32 arrays updated in place; stats (dict, optional): per skip reason the number of (point, view) pairs it dropped, "updated"
-    the number of pairs integrated."""
+    the number of pairs integrated.  points / valid (brick-major state): the three coordinate arrays, broadcastable to the
+    state's shape, instead of the axes' outer product, and the bool mask of the entries that are lattice points at all."""
     f32 = np.float32
-    px, py, pz = axes[0][:, None, None], axes[1][None, :, None], axes[2][None, None, :]
+    px, py, pz = (axes[0][:, None, None], axes[1][None, :, None], axes[2][None, None, :]) if points is None else points
     trunc = f32(trunc)
     for v in views:
         P = np.asarray(v.P, dtype=f32).reshape(12)
@@ -117,6 +126,8 @@ def integrate_host(tsdf, weight, color, axes, views, trunc, stats=None):
             measured = inside & (d > 0) & (d <= _F32_MAX)
             diff = d - cz
             ok = measured & (diff >= -trunc)
+            if valid is not None:
+                ok = ok & valid
             t = np.minimum(diff / trunc, f32(1.0))
             wn = weight + f32(1.0)
             tsdf[...] = np.where(ok, (tsdf * weight + t) / wn, tsdf)
@@ -451,9 +462,24 @@ class FusionVolume:
 
     grid: three coordinate arrays (any spacing), or (lo, hi, voxel).  trunc: truncation distance in world units (None: 4 x the
     largest axis step).  colors: also fuse the views' images.  backend "device" (HIP, state on `device`) or "host" (numpy fp32,
-    equal arrays).  integrate() may be called any number of times with any number of views."""
+    equal arrays).  integrate() may be called any number of times with any number of views.
+    sparse=True gives a SparseFusionVolume: the same mesh from state kept only near the measured surfaces."""
 
-    def __init__(self, grid, trunc=None, colors=False, backend="device", device=None):
+    def __new__(cls, *args, sparse=False, **kwargs):
+        sparse = sparse or (len(args) > 5 and args[5])
+        return object.__new__(SparseFusionVolume if sparse and cls is FusionVolume else cls)
+
+    def __init__(self, grid, trunc=None, colors=False, backend="device", device=None, sparse=False):
+        self._init_lattice(grid, trunc, backend, device)
+        if backend == "device":
+            self.tsdf = torch.zeros(self.shape, dtype=torch.float32, device=self.device)
+            self.weight = torch.zeros(self.shape, dtype=torch.float32, device=self.device)
+            self.color = torch.zeros(self.shape + (3,), dtype=torch.float32, device=self.device) if colors else None
+        else:
+            self.tsdf, self.weight = np.zeros(self.shape, np.float32), np.zeros(self.shape, np.float32)
+            self.color = np.zeros(self.shape + (3,), np.float32) if colors else None
+
+    def _init_lattice(self, grid, trunc, backend, device):
         if backend not in ("device", "host"):
             raise ValueError(f"FusionVolume: backend {backend!r} (device or host)")
         if len(grid) != 3:
@@ -477,14 +503,9 @@ class FusionVolume:
                 raise RuntimeError("FusionVolume(backend='device') needs a GPU (the SuRF hot path has no CPU fallback)")
             self.device = torch.device("cuda" if device is None else device)
             self.axes = [torch.from_numpy(a).to(self.device) for a in axes]
-            self.tsdf = torch.zeros(self.shape, dtype=torch.float32, device=self.device)
-            self.weight = torch.zeros(self.shape, dtype=torch.float32, device=self.device)
-            self.color = torch.zeros(self.shape + (3,), dtype=torch.float32, device=self.device) if colors else None
         else:
             self.device = None if device is None else torch.device(device)
             self.axes = axes
-            self.tsdf, self.weight = np.zeros(self.shape, np.float32), np.zeros(self.shape, np.float32)
-            self.color = np.zeros(self.shape + (3,), np.float32) if colors else None
 
     def _dev(self, x):
         if torch.is_tensor(x):
@@ -527,9 +548,14 @@ class FusionVolume:
             color = None if self.color is None else torch.from_numpy(self.color).to(dev)
             axes = [torch.from_numpy(a).to(dev) for a in self.axes]
         v, t = ops.marching_cubes(ops.fuse_lattice(tsdf, weight), float(isovalue), observed_only=True)
+        return self._mesh_to_host(v, t, None if color is None else ops.fuse_vertex_colors(v, color), axes)
+
+    @staticmethod
+    def _mesh_to_host(v, t, c, axes):
+        """Device mesh in lattice-index units (+ uint8 vertex colours or None) -> extract_mesh's numpy arrays, one copy."""
         parts = []
-        if color is not None:
-            c = ops.fuse_vertex_colors(v, color).reshape(-1)
+        if c is not None:
+            c = c.reshape(-1)
             parts = [torch.cat([c, c.new_zeros((-c.numel()) % 8)]).view(torch.int64)]
         # lattice-index units -> world: linear along the lattice edge, in float64 (exact for a uniform axis up to its fp32 values)
         cols = []
@@ -542,6 +568,197 @@ class FusionVolume:
         both = to_host(torch.cat([vw.reshape(-1).view(torch.int64), t.reshape(-1).to(torch.int64)] + parts))
         nv, nt = vw.numel(), t.numel()
         out = (both[:nv].view(torch.float64).numpy().reshape(-1, 3), both[nv:nv + nt].numpy().reshape(-1, 3))
-        if color is not None:
+        if c is not None:
             out += (both[nv + nt:].view(torch.uint8)[:nv].numpy().reshape(-1, 3),)
         return out
+
+
+# ---- brick-sparse fusion (csrc/fuse_sparse.hip): the same mesh from state kept only near the measured surfaces ----
+
+MARK_MARGIN = 2                  # lattice steps the index box of a pixel's pyramid is widened by (fuse_sparse.hip's header argues it)
+
+
+def mark_bricks_host(axes, views, trunc):
+    """The mark rule of fuse_sparse.hip's header comment in numpy fp32, one operation per operator in its order, over the pixels
+    of every view: the ascending int32 ids (bx nbp + by) nbp + bz, nbp = ceil(max(shape) / 8), of the bricks that can hold a
+    lattice point some view updates with diff < trunc, or a lattice neighbour of one.  axes: strictly increasing fp32 arrays."""
+    f32 = np.float32
+    n = [len(a) for a in axes]
+    nbp = (max(n) + 7) // 8
+    mark = np.zeros((nbp, nbp, nbp), bool)
+    trunc = f32(trunc)
+    for v in views:
+        L = lift_transform(v)
+        depth = _np(v.depth, f32)
+        with np.errstate(all="ignore"):
+            d = depth * f32(v.dscale)
+            yy, xx = np.nonzero((d > 0) & (d <= _F32_MAX))
+            d = d[yy, xx]
+            zs = (np.maximum(d - trunc, f32(0.0)), d + trunc)
+            ys = (yy.astype(f32) - f32(0.5), yy.astype(f32) + f32(0.5))
+            xs = (xx.astype(f32) - f32(0.5), xx.astype(f32) + f32(0.5))
+            lo = [np.full(d.shape, np.inf, f32) for _ in range(3)]
+            hi = [np.full(d.shape, -np.inf, f32) for _ in range(3)]
+            fin = [np.ones(d.shape, bool) for _ in range(3)]
+            for sz in zs:
+                for sy in ys:
+                    for sx in xs:
+                        qx, qy = sx * sz, sy * sz
+                        for k in range(3):
+                            X = ((L[3 * k] * qx + L[3 * k + 1] * qy) + L[3 * k + 2] * sz) + L[9 + k]
+                            fin[k] &= np.abs(X) <= _F32_MAX
+                            lo[k], hi[k] = np.fmin(lo[k], X), np.fmax(hi[k], X)
+        keep, cols = np.ones(d.shape, bool), []
+        for k in range(3):
+            i0 = np.where(fin[k], np.searchsorted(axes[k], lo[k], side="left"), 0)               # #{i : a[i] < lo}
+            i1 = np.where(fin[k], np.searchsorted(axes[k], hi[k], side="right") - 1, n[k] - 1)   # #{i : a[i] <= hi} - 1
+            i0, i1 = np.maximum(i0 - MARK_MARGIN, 0), np.minimum(i1 + MARK_MARGIN, n[k] - 1)
+            keep &= i0 <= i1
+            cols += [i0 >> 3, i1 >> 3]
+        for b in np.unique(np.stack(cols, axis=1)[keep], axis=0):
+            mark[b[0]:b[1] + 1, b[2]:b[3] + 1, b[4]:b[5] + 1] = True
+    return np.flatnonzero(mark.reshape(-1)).astype(np.int32)
+
+
+def integrate_bricks_host(tsdf, weight, color, bricks, axes, views, trunc, chunk=2048):
+    """integrate_host on brick-major state (fuse_integrate_bricks' layout): every view, in order, at every lattice point of the
+    listed bricks; points past the upper faces are never updated."""
+    n = [len(a) for a in axes]
+    nbp = (max(n) + 7) // 8
+    ids = np.asarray(bricks, np.int64)
+    for s in range(0, len(ids), chunk):
+        part = ids[s:s + chunk]
+        m = len(part)
+        origin = (part // (nbp * nbp), (part // nbp) % nbp, part % nbp)
+        idx = [origin[a][:, None] * 8 + np.arange(8) for a in range(3)]                     # (m, 8) lattice indices per axis
+        shapes = ((m, 8, 1, 1), (m, 1, 8, 1), (m, 1, 1, 8))
+        points = [axes[a][np.minimum(idx[a], n[a] - 1)].reshape(shapes[a]) for a in range(3)]
+        inside = [(idx[a] < n[a]).reshape(shapes[a]) for a in range(3)]
+        sl = slice(s * 512, (s + m) * 512)
+        integrate_host(tsdf[sl].reshape(m, 8, 8, 8), weight[sl].reshape(m, 8, 8, 8),
+                       None if color is None else color[sl].reshape(m, 8, 8, 8, 3), None, views, trunc, points=points,
+                       valid=inside[0] & inside[1] & inside[2])
+
+
+class SparseFusionVolume(FusionVolume):
+    """FusionVolume(..., sparse=True): the TSDF state in 8^3-point bricks near the measured surfaces only (mesh_band.hip's brick
+    table), for lattices the dense volume cannot hold - it takes 8 B per lattice point, 20 B with colours, and its mesh step
+    stops at 2^31 points.  extract_mesh() returns the dense volume's arrays, in the same order.
+
+    Why a subset is enough: a lattice point that no view updates with diff < trunc ends with tsdf == 1 exactly (or unobserved), and
+    at an isovalue in (-1, 1) an edge or cell carries geometry only when one of its corners has tsdf < 1.  The needed points are
+    those updated with diff < trunc, dilated by one lattice step; allocated are the bricks marked per depth pixel by the rule of
+    fuse_sparse.hip's header comment, a superset of the bricks that hold a needed point.  Every view is integrated over every
+    point of every allocated brick with the dense kernel's per-point arithmetic, so the state there equals the dense state.
+
+    Deferred integration: a brick allocated after a view was integrated would lack that view's free-space updates, so
+    integrate() only RECORDS its views - copies of depth and image on `device` (host backend: numpy), P and dscale; a 1080p view
+    with colours is 33 MB, 300 of them 10 GB - and the state is built at first use (finalize(), extract_mesh(), observed_share()
+    or any state attribute): bricks are allocated over all recorded views, then all views are integrated in order,
+    ops.FUSE_MAX_VIEWS per launch.  A later integrate() drops the state; it is rebuilt from all views at the next use.
+
+    Limits: strictly increasing axes, 2 <= max(shape) <= 8192, fewer than 2^31 / 512 allocated bricks, -1 < isovalue < 1.  The
+    brick table is dense, ceil(max(shape) / 8)^3 int32: 512 MB for a side of 4096.
+    State: bricks (int32 brick ids, ascending), table (brick id -> slot or -1), tsdf / weight (n_bricks * 512,) and color
+    (n_bricks * 512, 3), brick-major: slot * 512 + (lx << 6 | ly << 3 | lz); backend "host" is the numpy-fp32 mirror, equal arrays."""
+
+    def __init__(self, grid, trunc=None, colors=False, backend="device", device=None, sparse=True):
+        self._init_lattice(grid, trunc, backend, device)
+        if any(len(a) > 1 and not bool((np.diff(a) > 0).all()) for a in self.axes_host):
+            raise ValueError("FusionVolume(sparse=True): strictly increasing axes")
+        if not 2 <= max(self.shape) <= 8192:
+            raise ValueError("FusionVolume(sparse=True): 2 <= max(shape) <= 8192 (the band kernels' limit)")
+        self.colors = bool(colors)
+        self.res, self.nbp = ops.fuse_brick_dims(self.shape)
+        self._views, self._state = [], None
+
+    def integrate(self, views, stats=None):
+        """Records `views` (DepthViews, copied); they are fused, in order after the earlier ones, when the state is next used."""
+        views = [v if isinstance(v, DepthView) else DepthView(*v) for v in views]
+        if self.colors and any(v.image is None for v in views):
+            raise ValueError("FusionVolume.integrate: colours are fused but a view has no image")
+        if stats is not None:
+            raise ValueError("FusionVolume.integrate: stats are counted by the dense host backend")
+        for v in views:
+            if len(v.depth.shape) != 2 or (self.colors and tuple(v.image.shape) != tuple(v.depth.shape) + (3,)):
+                raise ValueError("FusionVolume.integrate: a view holds depth (H, W) and image (H, W, 3)")
+            keep = self._copy_dev if self.backend == "device" else (lambda x: np.array(_np(x), dtype=np.float32, order="C"))
+            self._views.append(DepthView(np.array(_np(v.P), dtype=np.float32).reshape(3, 4), keep(v.depth), float(v.dscale),
+                                         keep(v.image) if self.colors else None))
+        self.n_views += len(views)
+        self._state = None
+
+    def _copy_dev(self, x):
+        y = self._dev(x)
+        return y.clone() if torch.is_tensor(x) and y.data_ptr() == x.data_ptr() else y
+
+    def finalize(self):
+        """Builds the state from all recorded views (a no-op when it is current).  Returns self."""
+        if self._state is not None:
+            return self
+        views, nt = self._views, self.nbp ** 3
+        if self.backend == "device":
+            mark = torch.zeros(nt, dtype=torch.uint8, device=self.device)
+            for v in views:
+                ops.fuse_mark_bricks(mark, self.axes, lift_transform(v), v.depth, v.dscale, self.trunc)
+            table, bricks = ops.fuse_assign_bricks(mark)
+            m = int(bricks.shape[0])
+            tsdf = torch.zeros(m * 512, dtype=torch.float32, device=self.device)
+            weight = torch.zeros(m * 512, dtype=torch.float32, device=self.device)
+            color = torch.zeros(m * 512, 3, dtype=torch.float32, device=self.device) if self.colors else None
+            for s in range(0, len(views), ops.FUSE_MAX_VIEWS):
+                ops.fuse_integrate_bricks(tsdf, weight, color, bricks, self.axes,
+                                          [(v.P, v.depth, v.dscale, v.image) for v in views[s:s + ops.FUSE_MAX_VIEWS]], self.trunc)
+        else:
+            bricks = mark_bricks_host(self.axes, views, self.trunc)
+            m = len(bricks)
+            if m * 512 >= 2 ** 31:
+                raise ValueError("FusionVolume(sparse=True): 2^31 / 512 allocated bricks or more")
+            table = np.full(nt, -1, np.int32)
+            table[bricks] = np.arange(m, dtype=np.int32)
+            tsdf, weight = np.zeros(m * 512, np.float32), np.zeros(m * 512, np.float32)
+            color = np.zeros((m * 512, 3), np.float32) if self.colors else None
+            integrate_bricks_host(tsdf, weight, color, bricks, self.axes, views, self.trunc)
+        self._state = (bricks, table, tsdf, weight, color)
+        return self
+
+    bricks = property(lambda self: self.finalize()._state[0])
+    table = property(lambda self: self.finalize()._state[1])
+    tsdf = property(lambda self: self.finalize()._state[2])
+    weight = property(lambda self: self.finalize()._state[3])
+    color = property(lambda self: self.finalize()._state[4])
+
+    @property
+    def n_bricks(self):
+        return int(self.bricks.shape[0])
+
+    def allocated_share(self):
+        """Allocated bricks over the bricks of the lattice."""
+        return self.n_bricks / float(np.prod([(n + 7) // 8 for n in self.shape]))
+
+    def state_bytes(self):
+        """Bytes of the built state: tsdf, weight (and colours) of the allocated bricks, the brick list and the brick table."""
+        return self.n_bricks * (512 * (20 if self.colors else 8) + 4) + 4 * self.nbp ** 3
+
+    def extract_mesh(self, isovalue=0.0):
+        """FusionVolume.extract_mesh's arrays, the same mesh in the same order, for -1 < isovalue < 1 (ValueError otherwise: the
+        allocation covers only what such an isovalue can cut).  Runs on the GPU whatever the backend."""
+        if not -1.0 < float(isovalue) < 1.0:
+            raise ValueError("FusionVolume(sparse=True).extract_mesh: -1 < isovalue < 1")
+        self.finalize()
+        if self.n_bricks == 0:
+            empty = (np.zeros((0, 3), np.float64), np.zeros((0, 3), np.int64))
+            return empty + ((np.zeros((0, 3), np.uint8),) if self.colors else ())
+        bricks, table, tsdf, weight, color = self._state
+        axes = self.axes
+        if self.backend == "host":
+            if not torch.cuda.is_available():
+                raise RuntimeError("FusionVolume.extract_mesh: marching cubes runs on the GPU (the SuRF hot path has no CPU fallback)")
+            dev = torch.device("cuda") if self.device is None else self.device
+            bricks, table, tsdf, weight = (torch.from_numpy(x).to(dev) for x in (bricks, table, tsdf, weight))
+            color = None if color is None else torch.from_numpy(color).to(dev)
+            axes = [torch.from_numpy(a).to(dev) for a in self.axes]
+        band = ops.Band(self.res, table, None, bricks, ops.fuse_band_values(tsdf, weight), {}, shape=self.shape)
+        v, t = ops.marching_cubes_band(band, float(isovalue), observed_only=True)
+        c = None if color is None else ops.fuse_vertex_colors_bricks(v, color, table, self.shape)
+        return self._mesh_to_host(v, t, c, axes)

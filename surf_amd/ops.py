@@ -1909,6 +1909,122 @@ def fuse_vertex_colors(vertices, color):
     return out
 
 
+# ---- brick-sparse fusion (fuse_sparse.hip): the same state in the 8^3-point bricks near the measured surfaces only ----
+
+def fuse_brick_dims(shape):
+    """(res, nbp) of a lattice (nx, ny, nz) in the band layout: the side of the cube it is embedded in (its longest axis) and the
+    bricks per axis of that cube's table (nbp^3 entries, brick ids (bx nbp + by) nbp + bz)."""
+    res = max(int(n) for n in shape)
+    return res, (res + 7) // 8
+
+
+def _chk_fuse_axes(axes):
+    if len(axes) != 3:
+        raise ValueError("fuse: three axis arrays")
+    for a, name in zip(axes, ("ax", "ay", "az")):
+        _chk(a, torch.float32, name)
+        if a.dim() != 1 or a.numel() < 1:
+            raise ValueError(f"fuse: {name} is a 1-d array of coordinates")
+    return tuple(int(a.numel()) for a in axes)
+
+
+def fuse_mark_bricks(mark, axes, lift, depth, dscale, trunc):
+    """One view's marks: mark (nbp^3 bytes of the lattice's brick table, see fuse_brick_dims) gets a 1 at every brick that can
+    hold a lattice point the view updates within the truncation distance, or a neighbour of one - a conservative superset, the
+    rule is written out in fuse_sparse.hip's header comment.  axes: the three device coordinate arrays, strictly increasing;
+    lift: fusion.lift_transform(view) (12 fp32 on the host); depth (H, W) fp32 device tensor."""
+    nx, ny, nz = _chk_fuse_axes(axes)
+    _chk(mark, torch.uint8, "mark")
+    _chk(depth, torch.float32, "depth")
+    if depth.dim() != 2:
+        raise ValueError("fuse_mark_bricks: depth (H, W)")
+    if mark.numel() != fuse_brick_dims((nx, ny, nz))[1] ** 3:
+        raise ValueError("fuse_mark_bricks: mark holds one byte per brick of the table")
+    if depth.numel() == 0:
+        return
+    lift = np.ascontiguousarray(np.asarray(lift, dtype=np.float32).reshape(12))
+    H, W = (int(v) for v in depth.shape)
+    _lib.lib().surf_fuse_mark_bricks(_p(depth), H, W, ctypes.c_float(float(dscale)), _np_ptr(lift), _p(axes[0]), _p(axes[1]),
+                                     _p(axes[2]), nx, ny, nz, ctypes.c_float(float(trunc)), _p(mark), _stream())
+
+
+def fuse_assign_bricks(mark):
+    """(table (nbp^3,) int32: brick id -> slot or -1, bricks (n_slots,) int32: the marked brick ids, ascending) of a mark array;
+    the marks are cleared.  One host read (the count)."""
+    _chk(mark, torch.uint8, "mark")
+    ids = compact(mark)
+    m = int(ids.shape[0])
+    table = torch.full((mark.numel(),), -1, dtype=torch.int32, device=mark.device)
+    bricks = torch.empty(m, dtype=torch.int32, device=mark.device)
+    if m:
+        _lib.lib().surf_band_assign(_p(ids), m, 0, _p(table), _p(bricks), _p(mark), _stream())
+    return table, bricks
+
+
+def fuse_integrate_bricks(tsdf, weight, color, bricks, axes, views, trunc):
+    """fuse_integrate on brick-major state: tsdf / weight (n_slots * 512,) and color (n_slots * 512, 3) or None are updated in
+    place with `views` (fuse_integrate's tuples, at most FUSE_MAX_VIEWS, in order) at every lattice point of the listed bricks;
+    points past the upper faces are never updated.  The per-point arithmetic is fuse.hip's."""
+    nx, ny, nz = _chk_fuse_axes(axes)
+    _chk(bricks, torch.int32, "bricks")
+    _chk(tsdf, torch.float32, "tsdf")
+    _chk(weight, torch.float32, "weight")
+    m = int(bricks.shape[0])
+    if tsdf.numel() != m * 512 or weight.numel() != m * 512:
+        raise ValueError("fuse_integrate_bricks: tsdf and weight hold 512 points per brick")
+    if color is not None:
+        _chk(color, torch.float32, "color")
+        if color.numel() != m * 512 * 3:
+            raise ValueError("fuse_integrate_bricks: color holds 512 x 3 values per brick")
+    n = len(views)
+    if n == 0 or m == 0:
+        return
+    P = np.empty((n, 12), dtype=np.float32)
+    hw = np.empty((n, 2), dtype=np.int32)
+    dscale = np.empty(n, dtype=np.float32)
+    depths, images = [], []
+    for v, (Pv, depth, ds, image) in enumerate(views):
+        _chk(depth, torch.float32, f"views[{v}].depth")
+        if depth.dim() != 2:
+            raise ValueError(f"fuse_integrate_bricks: views[{v}].depth (H, W)")
+        P[v] = np.asarray(Pv, dtype=np.float32).reshape(12)
+        hw[v] = depth.shape
+        dscale[v] = ds
+        depths.append(depth)
+        if color is not None:
+            if image is None:
+                raise ValueError(f"fuse_integrate_bricks: colours are fused but views[{v}] has no image")
+            _chk(image, torch.float32, f"views[{v}].image")
+            if tuple(image.shape) != tuple(depth.shape) + (3,):
+                raise ValueError(f"fuse_integrate_bricks: views[{v}].image (H, W, 3)")
+            images.append(image)
+    _lib.lib().surf_fuse_integrate_bricks(_p(tsdf), _p(weight), _p(color), _p(bricks), m, _p(axes[0]), _p(axes[1]), _p(axes[2]), nx,
+                                          ny, nz, _np_ptr(P), _ptr_array(depths), _ptr_array(images) if images else None,
+                                          _np_ptr(hw), _np_ptr(dscale), n, ctypes.c_float(float(trunc)), _stream())
+
+
+def fuse_band_values(tsdf, weight):
+    """The band values of brick-major state: u = -tsdf where weight > 0, NaN elsewhere (fuse_lattice on the flat arrays)."""
+    return fuse_lattice(tsdf.reshape(-1), weight.reshape(-1))
+
+
+def fuse_vertex_colors_bricks(vertices, color, table, shape):
+    """fuse_vertex_colors on brick-major colours (n_slots * 512, 3) of the lattice `shape`, read through the brick table."""
+    _chk(vertices, torch.float64, "vertices")
+    _chk(color, torch.float32, "color")
+    _chk(table, torch.int32, "table")
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or color.dim() != 2 or color.shape[1] != 3:
+        raise ValueError("fuse_vertex_colors_bricks: vertices (V, 3), color (n_slots * 512, 3)")
+    nx, ny, nz = (int(v) for v in shape)
+    if table.numel() != fuse_brick_dims(shape)[1] ** 3:
+        raise ValueError("fuse_vertex_colors_bricks: table holds one entry per brick")
+    n = int(vertices.shape[0])
+    out = torch.empty(n, 3, dtype=torch.uint8, device=vertices.device)
+    if n:
+        _lib.lib().surf_fuse_vertex_colors_bricks(_p(vertices), n, _p(color), _p(table), nx, ny, nz, _p(out), _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # multi-view geometric consistency of depth maps (depth_filter.hip): which pixels do enough other views agree with
 # ------------------------------------------------------------------------------------------------
@@ -2130,10 +2246,12 @@ def band_screen(uc, caxes, resolution, isovalue, margin):
 class Band:
     """The evaluated narrow band of a resolution^3 lattice (mesh_band.hip's state): table (nbp^3 int32: brick id -> slot or -1),
     is_cell (nbp^3 bytes: the brick's cells are meshed), bricks (slot -> brick id), values (slot * 512 + local point: u = -sdf;
-    NaN past the upper faces) and the growth statistics."""
+    NaN past the upper faces) and the growth statistics.  shape (fused bands only): the lattice (nx, ny, nz) embedded in the
+    cube of side resolution = max(shape); such a band has no is_cell and is meshed with observed_only=True."""
 
-    def __init__(self, resolution, table, is_cell, bricks, values, stats):
+    def __init__(self, resolution, table, is_cell, bricks, values, stats, shape=None):
         self.resolution, self.table, self.is_cell, self.bricks, self.values, self.stats = resolution, table, is_cell, bricks, values, stats
+        self.shape = shape
 
     @property
     def n_slots(self):
@@ -2196,10 +2314,12 @@ def band_grow(resolution, isovalue, mark, evaluate):
     return Band(n, table, is_cell, bricks[:n_slots], values[:n_slots * 512], stats)
 
 
-def marching_cubes_band(band, isovalue=0.0):
+def marching_cubes_band(band, isovalue=0.0, observed_only=False):
     """marching_cubes on a Band: (vertices (nv, 3) float64, triangles (nt, 3) int32) device tensors in lattice-index units, the
     arrays marching_cubes returns on the dense lattice (same order) for every surface component that has a cell brick.
-    Two host syncs size the outputs (number of flagged points, then vertex / triangle totals)."""
+    Two host syncs size the outputs (number of flagged points, then vertex / triangle totals).
+    observed_only (fused bands: band.shape is the lattice, NaN = unobserved or not allocated): surf_band_classify_observed - the
+    rule of marching_cubes(observed_only=True), every allocated brick meshed - and the same drop of unreferenced vertices."""
     L = _lib.lib()
     dev = band.values.device
     n, ns = band.resolution, band.n_slots
@@ -2208,7 +2328,13 @@ def marching_cubes_band(band, isovalue=0.0):
     if ns == 0:
         return empty
     flags = torch.empty(ns * 512, dtype=torch.uint8, device=dev)
-    L.surf_band_classify(_p(band.values), _p(band.table), _p(band.is_cell), _p(band.bricks), ns, n, iso, _p(flags), _stream())
+    if observed_only:
+        if band.shape is None or max(band.shape) != n:
+            raise ValueError("marching_cubes_band: observed_only needs band.shape with max(shape) == resolution")
+        nx, ny, nz = (int(v) for v in band.shape)
+        L.surf_band_classify_observed(_p(band.values), _p(band.table), _p(band.bricks), ns, nx, ny, nz, iso, _p(flags), _stream())
+    else:
+        L.surf_band_classify(_p(band.values), _p(band.table), _p(band.is_cell), _p(band.bricks), ns, n, iso, _p(flags), _stream())
     pos = compact(flags)
     m = int(pos.shape[0])
     if m == 0:
@@ -2226,6 +2352,8 @@ def marching_cubes_band(band, isovalue=0.0):
     vbase = torch.empty(ns * 512, dtype=torch.int32, device=dev)
     L.surf_band_emit(_p(band.values), _p(band.table), n, iso, _p(flags), _p(keys), _p(pos), m, _p(ws), _p(vbase), _p(vertices),
                      _p(triangles), _stream())
+    if observed_only:
+        return clean_update_faces(vertices, triangles, torch.ones(n_t, dtype=torch.uint8, device=dev))
     return vertices, triangles
 
 
