@@ -999,6 +999,49 @@ int surf_points_lift(const float* cand_r, int H, int W, float dscale_r, const in
                      const int64_t* kept, int64_t n_kept, const float* h_lift, const float* image, int view, float* points,
                      uint8_t* colors, int32_t* origin, void* stream);
 
+/*
+ * Tanks and Temples / ETH3D F-score evaluation on the device (surf_amd/evaluation/fscore.py, device="gpu"; fscore.hip).  fp64
+ * throughout, in the host path's operation order: the transform, the crop, the voxel means and the nearest distances / indices
+ * equal the numpy / scikit-learn path's arrays.  Added under SURF_ABI_VERSION 41 without a bump, like the entry points above.
+ * Points are (n,3) fp64 on the device; n >= 2^31 (int32 point indices) or a grid of more than 2^21 cells along an axis is
+ * SURF_E_LIMIT, never a wrapped index.
+ *   surf_fscore_transform: out = R p + t with HOST h_T (16) fp64, a row-major 4x4 whose last row is not read:
+ *     out[k] = ((R[k,0]*x + R[k,1]*y) + R[k,2]*z) + t[k].  out must not overlap points.
+ *   surf_fscore_crop: keep (n) uint8 = axis_min <= p[axis] <= axis_max and p inside polygon (n_polygon >= 3 vertices, (n_polygon,2)
+ *     fp64 on the DEVICE: the coordinates (u, v) along the two other axes in increasing order) by the crossing number over the
+ *     edges (i, j = i - 1): ((v_i > v) != (v_j > v)) and u < (u_j - u_i) * (v - v_i) / (v_j - v_i) + u_i.
+ *   surf_fscore_voxel_keys: keys[i] = (cx << 42) | (cy << 21) | cz of the cell floor((p - origin) / voxel), origin = h_lo - voxel/2,
+ *     with HOST h_lo (3), h_hi (3) the per-axis minimum and maximum of the points (Open3D's voxel_down_sample grid); a box that
+ *     needs more than 2^21 cells along an axis is SURF_E_LIMIT.
+ *   surf_fscore_voxel_mean: out (n_voxels,3) = per voxel the sum of its members, added one after the other in the order given,
+ *     divided by their number.  order (n) int64 = the points' indices sorted by key (a STABLE sort: input order inside a voxel),
+ *     segment_start (n_voxels+1) int64 = the first position of every voxel in order.  A voxel may hold any number of points.
+ *   surf_fscore_nearest: surf_dtu_nearest that also reports WHICH point: sorted_index (r) int32 = the index in the caller's order of
+ *     every row of sorted_ref; index (m) int64 = that of the nearest reference point, -1 where out is +inf.  Equal squared
+ *     distances go to the smaller index.
+ *   surf_fscore_icp_sums / _cov: the two reductions of one point-to-point ICP step over the pairs (source[i], target[index[i]]),
+ *     index[i] in [0, n_target) (any other value: no pair).  _sums: out (8) = [pairs, sum of source (3), sum of target (3), sum of
+ *     dist*dist]; _cov: out (9) row-major H[r][c] = sum (source[r] - cs[r]) * (target[c] - ct[c]) with HOST h_centroids (6) =
+ *     cs then ct.  partials: device scratch of SURF_FSCORE_ICP_SLOTS * 9 fp64.  Workgroup w of min(ceil(n / 256),
+ *     SURF_FSCORE_ICP_SLOTS) writes its sums to slot w, then one workgroup adds the slots in slot order: no float atomics, the same
+ *     bits on every run.
+ */
+#define SURF_FSCORE_ICP_SLOTS 1024
+int surf_fscore_transform(const double* points, int64_t n, const double* h_T, double* out, void* stream);
+int surf_fscore_crop(const double* points, int64_t n, int axis, double axis_min, double axis_max, const double* polygon, int n_polygon,
+                     uint8_t* keep, void* stream);
+int surf_fscore_voxel_keys(const double* points, int64_t n, const double* h_lo, const double* h_hi, double voxel, int64_t* keys,
+                           void* stream);
+int surf_fscore_voxel_mean(const double* points, int64_t n, const int64_t* order, const int64_t* segment_start, int64_t n_voxels,
+                           double* out, void* stream);
+int surf_fscore_nearest(const double* queries, int64_t m, const double* sorted_ref, const int32_t* sorted_index,
+                        const int32_t* cell_start, double lo_x, double lo_y, double lo_z, double cell, int64_t nx, int64_t ny, int64_t nz,
+                        double max_dist, double* out, int64_t* index, void* stream);
+int surf_fscore_icp_sums(const double* source, const double* target, int64_t n_target, const int64_t* index, const double* dist,
+                         int64_t n, double* partials, double* out, void* stream);
+int surf_fscore_icp_cov(const double* source, const double* target, int64_t n_target, const int64_t* index, int64_t n,
+                        const double* h_centroids, double* partials, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

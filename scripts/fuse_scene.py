@@ -22,6 +22,10 @@ reads their scale_mats) at --voxel_mm world units per step, or --resolution poin
 With --sparse the lattice is brick-sparse (fusion.FusionVolume(sparse=True), csrc/fuse_sparse.hip): the same mesh from state kept
 only near the measured surfaces, for lattices of 2^31 points and more (a dense lattice of that size exits at once); the record
 gains `sparse`, `bricks`, `allocated_share` and `state_bytes`, and ms.finalize (allocation + integration of the recorded views).
+With --scene NAME instead of --scan N the conf's own dataset (e.g. TanksDataset) is read for that scene and the outputs are named
+after it (<NAME>.ply, <NAME>_points.ply, fused_<NAME>.json; the record carries `scene`); --tnt_dir D [--tau X] [--no_refine] then
+scores the mesh (and the cloud) with the Tanks and Temples protocol (evaluation.fscore.evaluate_scene): precision, recall, fscore
+(pcd_* for the cloud) and ms.evaluate_fscore.  --clean_mesh and --eval_dir are DTU's protocol and stay with --scan.
 Measurement harness like scripts/dtu_chamfer.py: one scan per call, no logging framework, no resume logic."""
 import argparse
 import json
@@ -40,7 +44,11 @@ def parse_args(argv=None):
     ap.add_argument("--conf", required=True, help="HOCON conf with `model` and `val_dataset` blocks (the reference's confs/*.conf)")
     ap.add_argument("--ckpt", default=None, help="checkpoint saved by runner.py (`model` key) - omitted: seeded random weights")
     ap.add_argument("--data_dir", default=None, help="overrides val_dataset.data_dir")
-    ap.add_argument("--scan", type=int, default=24)
+    which = ap.add_mutually_exclusive_group()
+    which.add_argument("--scan", type=int, default=24)
+    which.add_argument("--scene", default=None,
+                       help="a scene by name (Tanks and Temples: Barn, Family, ...) of the conf's own dataset_name, instead of DTU's "
+                            "scan<N>; the outputs are named after it")
     ap.add_argument("--ref_views", type=int, nargs="+", default=None, help="reference views to fuse (default: val_dataset.ref_view)")
     size = ap.add_mutually_exclusive_group()
     size.add_argument("--voxel_mm", type=float, default=None, help="lattice step in world units (DTU: millimetres)")
@@ -74,6 +82,11 @@ def parse_args(argv=None):
     ap.add_argument("--patch_size", type=float, default=60)
     ap.add_argument("--max_dist", type=float, default=20)
     ap.add_argument("--shuffle_seed", type=int, default=0)
+    ap.add_argument("--tnt_dir", default=None,
+                    help="Tanks and Temples ground truth (<scene>/<scene>.ply, .json, _trans.txt): also report precision, recall and "
+                         "F-score of the mesh (and of the cloud with --point_cloud), evaluation/fscore.py; needs --scene")
+    ap.add_argument("--tau", type=float, default=None, help="F-score distance threshold (default: the benchmark's value for the scene)")
+    ap.add_argument("--no_refine", action="store_true", help="F-score: use <scene>_trans.txt as it is, no ICP")
     ap.add_argument("--out_dir", default="./outputs")
     ap.add_argument("--sdf_precision", default=None, choices=["f32", "bf16x3", "f16x2"])
     ap.add_argument("--logit_override", default=None, choices=["sphere"],
@@ -92,13 +105,20 @@ def run(args, state=None):
     from surf_amd.surf import SuRF
 
     dev = torch.device(args.device)
+    # a caller may build the Namespace by hand without the scene / F-score attributes
+    scene, tnt_dir = getattr(args, "scene", None), getattr(args, "tnt_dir", None)
+    name = scene if scene is not None else f"scan{args.scan}"
+    if scene is not None and (args.clean_mesh or args.eval_dir is not None):
+        raise SystemExit("fuse_scene: --clean_mesh and --eval_dir are DTU's protocol and need --scan, not --scene")
+    if tnt_dir is not None and scene is None:
+        raise SystemExit("fuse_scene: --tnt_dir needs --scene")
     if args.clean_mesh and args.dtu_test_dir is None:
         raise SystemExit("fuse_scene: --clean_mesh needs --dtu_test_dir")
     cfg = C.parse_file(args.conf)
     dconf = cfg["val_dataset"]
     if args.data_dir is not None:
         dconf["data_dir"] = args.data_dir
-    dconf["scene"] = [f"scan{args.scan}"]
+    dconf["scene"] = [name]
     if args.ref_views is not None:
         dconf["ref_view"] = list(args.ref_views)
     mconf = cfg["model"]
@@ -108,7 +128,7 @@ def run(args, state=None):
     t0 = time.perf_counter()
     loader, _, dataset = get_loader(dconf, "val", False, num_workers=0)
     if len(dataset) < 1:
-        raise SystemExit(f"fuse_scene: no validation item for scan{args.scan} under {dconf['data_dir']}")
+        raise SystemExit(f"fuse_scene: no validation item for {name} under {dconf['data_dir']}")
     torch.manual_seed(0)
     model = SuRF(mconf)
     if args.ckpt is not None:
@@ -167,7 +187,7 @@ def run(args, state=None):
         cloud = fusion.fuse_points(cloud_views, args.min_consistent, args.consistency_px, args.consistency_rel, sources=near,
                                    device=dev)
         ms["points"] = 1e3 * (time.perf_counter() - t0)
-        points_path = os.path.join(args.out_dir, "meshes", "fused", f"scan{args.scan}_points.ply")
+        points_path = os.path.join(args.out_dir, "meshes", "fused", f"{name}_points.ply")
         mesh_io.write_ply_points(points_path, cloud.points, cloud.colors)
         cloud_views.clear()
     filtered = None
@@ -206,14 +226,14 @@ def run(args, state=None):
         colors = None if colors is None else colors[kept]
         ms["clean"] = 1e3 * (time.perf_counter() - t0)
     t0 = time.perf_counter()
-    mesh_path = os.path.join(args.out_dir, "meshes", "fused", f"scan{args.scan}.ply")
+    mesh_path = os.path.join(args.out_dir, "meshes", "fused", f"{name}.ply")
     mesh_io.write_ply(mesh_path, v, t, colors=colors)
     ms["write"] = 1e3 * (time.perf_counter() - t0)
     if state is not None:
         state.update(model=model, volume=volume, vertices=v, triangles=t, colors=colors)
         if cloud is not None:
             state.update(cloud=cloud)
-    rec = {"scan": args.scan, "views_fused": volume.n_views, "lattice": list(volume.shape), "voxel": voxel, "trunc": volume.trunc,
+    rec = {("scan" if scene is None else "scene"): (args.scan if scene is None else scene), "views_fused": volume.n_views, "lattice": list(volume.shape), "voxel": voxel, "trunc": volume.trunc,
            "observed_share": volume.observed_share(), "vertices": int(len(v)), "triangles": int(len(t)), "depth": args.depth,
            "colors": bool(args.colors), "cleaned": bool(args.clean_mesh), "mesh": mesh_path, "ms": ms}
     if args.sparse:                                     # without the flag the record is what it was
@@ -236,7 +256,17 @@ def run(args, state=None):
                                                        rng=np.random.default_rng(args.shuffle_seed), device=args.eval_device)
             ms["evaluate_points"] = 1e3 * (time.perf_counter() - t0)
             rec.update(pcd_d2s=d2s, pcd_s2d=s2d, pcd_chamfer=overall)
-    with open(os.path.join(args.out_dir, f"fused_scan{args.scan}.json"), "w") as f:
+    if tnt_dir is not None:
+        from surf_amd.evaluation import fscore
+        t0 = time.perf_counter()
+        kw = dict(tau=getattr(args, "tau", None), refine=not getattr(args, "no_refine", False), device=args.eval_device)
+        res = fscore.evaluate_scene(mesh_path, tnt_dir, scene, mode="mesh", **kw)
+        rec.update(precision=res["precision"], recall=res["recall"], fscore=res["fscore"], tau=res["tau"])
+        if cloud is not None:
+            res = fscore.evaluate_scene(points_path, tnt_dir, scene, mode="pcd", **kw)
+            rec.update(pcd_precision=res["precision"], pcd_recall=res["recall"], pcd_fscore=res["fscore"])
+        ms["evaluate_fscore"] = 1e3 * (time.perf_counter() - t0)
+    with open(os.path.join(args.out_dir, f"fused_{name}.json"), "w") as f:
         json.dump(rec, f)
     return rec
 

@@ -1,1 +1,1 @@
-"""Offline evaluation: DTU Chamfer distance and mask / visibility based mesh cleaning."""
+"""Offline evaluation: DTU Chamfer distance, mask / visibility based mesh cleaning, and the Tanks and Temples F-score."""

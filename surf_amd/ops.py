@@ -1408,6 +1408,174 @@ def nearest_dist_capped(queries, ref, max_dist):
     return out
 
 
+# ---- F-score evaluation (fscore.hip): transform, polygon crop, voxel mean, nearest with index, the ICP reductions, all fp64 ----
+
+FSCORE_ICP_SLOTS = 1024          # SURF_FSCORE_ICP_SLOTS of include/surf_hip.h
+
+
+def _chk_points(t, name):
+    _chk(t, torch.float64, name)
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"{name}: expected (n, 3), got {tuple(t.shape)}")
+    if t.shape[0] > 2 ** 31 - 1:
+        raise ValueError(f"{name}: {t.shape[0]} points exceed int32 indexing")
+    return t
+
+
+def fscore_transform(points, T):
+    """R p + t of (n, 3) float64 device points with the HOST 4x4 T, as ((R[k,0]*x + R[k,1]*y) + R[k,2]*z) + t[k]."""
+    _chk_points(points, "points")
+    T = np.ascontiguousarray(np.asarray(T, dtype=np.float64).reshape(4, 4))
+    out = torch.empty_like(points)
+    if points.shape[0] == 0:
+        return out
+    _lib.lib().surf_fscore_transform(_p(points), points.shape[0], _np_ptr(T), _p(out), _stream())
+    return out
+
+
+def fscore_crop(points, axis, axis_min, axis_max, polygon_uv):
+    """keep (n,) bool: axis_min <= p[axis] <= axis_max and (u, v) = the two other coordinates inside polygon_uv (k, 2) float64
+    (a device tensor) by the crossing-number rule of fscore.hip."""
+    _chk_points(points, "points")
+    _chk(polygon_uv, torch.float64, "polygon_uv")
+    if polygon_uv.dim() != 2 or polygon_uv.shape[1] != 2 or polygon_uv.shape[0] < 3:
+        raise ValueError(f"polygon_uv: expected (k >= 3, 2), got {tuple(polygon_uv.shape)}")
+    if axis not in (0, 1, 2):
+        raise ValueError(f"fscore_crop: axis must be 0, 1 or 2, got {axis}")
+    n = points.shape[0]
+    keep = torch.empty(n, dtype=torch.uint8, device=points.device)
+    if n == 0:
+        return keep.bool()
+    _lib.lib().surf_fscore_crop(_p(points), n, int(axis), float(axis_min), float(axis_max), _p(polygon_uv), polygon_uv.shape[0],
+                                _p(keep), _stream())
+    return keep.bool()
+
+
+def fscore_voxel_mean(points, voxel):
+    """One point per occupied cell of the grid of `voxel` at min(points) - voxel / 2, in ascending (x << 42) | (y << 21) | z order:
+    the members' sum in input order over their number ((m, 3) float64).  One host sync for the box, one for m."""
+    _chk_points(points, "points")
+    n = points.shape[0]
+    dev = points.device
+    if n == 0:
+        return torch.empty(0, 3, dtype=torch.float64, device=dev)
+    if not (voxel > 0 and np.isfinite(voxel)):
+        raise ValueError(f"fscore_voxel_mean: voxel must be finite and > 0, got {voxel}")
+    L = _lib.lib()
+    lo = np.array(points.amin(0).tolist())
+    hi = np.array(points.amax(0).tolist())
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    L.surf_fscore_voxel_keys(_p(points), n, _np_ptr(lo), _np_ptr(hi), float(voxel), _p(keys), _stream())
+    skeys, order = torch.sort(keys, stable=True)              # stable: a voxel lists its points in input order
+    _, counts = torch.unique_consecutive(skeys, return_counts=True)
+    m = counts.shape[0]
+    seg = torch.zeros(m + 1, dtype=torch.int64, device=dev)
+    seg[1:] = torch.cumsum(counts, 0)
+    out = torch.empty(m, 3, dtype=torch.float64, device=dev)
+    L.surf_fscore_voxel_mean(_p(points), n, _p(order), _p(seg), m, _p(out), _stream())
+    return out
+
+
+class NearestTable:
+    """The dense cell table of nearest_dist_capped over one reference cloud, kept for several query sets (an ICP round asks the
+    same target twenty times).  cells_per_point / cell / dims say how dense it came out.  The sizing is nearest_dist_capped's,
+    repeated here so that the DTU evaluation's path stays as it is."""
+
+    def __init__(self, ref):
+        _chk_points(ref, "ref")
+        r = ref.shape[0]
+        if r == 0:
+            raise ValueError("NearestTable: empty reference")
+        dev = ref.device
+        lo, ext = _box(ref)
+        pad = max(ext) * 1e-3 or 1.0                  # flat or single-point clouds still get a box of some volume
+        vol = (ext[0] + pad) * (ext[1] + pad) * (ext[2] + pad)
+        cell = max((vol / (4.0 * r)) ** (1.0 / 3.0), max(ext) / (THIN_AXIS_CELLS - 2))   # about four cells per reference point
+        while True:
+            dims = [int(e // cell) + 1 for e in ext]
+            if dims[0] * dims[1] * dims[2] <= NEAREST_MAX_CELLS:
+                break
+            cell *= 1.25
+        ncell = dims[0] * dims[1] * dims[2]
+        keys = torch.empty(r, dtype=torch.int64, device=dev)
+        _lib.lib().surf_dtu_cell_keys(_p(ref), r, lo[0], lo[1], lo[2], cell, dims[0], dims[1], dims[2], _p(keys), _stream())
+        skeys, order = torch.sort(keys)
+        self.cstart = torch.zeros(ncell + 1, dtype=torch.int32, device=dev)
+        self.cstart[1:] = torch.cumsum(torch.bincount(skeys, minlength=ncell), 0)
+        self.sref = ref[order].contiguous()
+        self.sidx = order.to(torch.int32)
+        self.lo, self.cell, self.dims, self.r = lo, cell, dims, r
+        self.cells_per_point = ncell / r
+
+    def query(self, queries, max_dist):
+        _chk_points(queries, "queries")
+        if not (max_dist > 0 and np.isfinite(max_dist)):
+            raise ValueError(f"nearest_capped_index: max_dist must be finite and > 0, got {max_dist}")
+        m = queries.shape[0]
+        dist = torch.empty(m, dtype=torch.float64, device=queries.device)
+        index = torch.empty(m, dtype=torch.int64, device=queries.device)
+        if m:
+            lo, d = self.lo, self.dims
+            _lib.lib().surf_fscore_nearest(_p(queries), m, _p(self.sref), _p(self.sidx), _p(self.cstart), lo[0], lo[1], lo[2],
+                                           self.cell, d[0], d[1], d[2], float(max_dist), _p(dist), _p(index), _stream())
+        return dist, index
+
+
+def nearest_capped_index(queries, ref, max_dist):
+    """nearest_dist_capped plus WHICH reference point: (dist (m,) float64, +inf where >= max_dist; index (m,) int64 into ref, -1
+    there).  Equal squared distances go to the smaller index.  ref may be a NearestTable."""
+    _chk_points(queries, "queries")
+    m = queries.shape[0]
+    dev = queries.device
+    if not (max_dist > 0 and np.isfinite(max_dist)):
+        raise ValueError(f"nearest_capped_index: max_dist must be finite and > 0, got {max_dist}")
+    if not isinstance(ref, NearestTable):
+        _chk_points(ref, "ref")
+        if m == 0 or ref.shape[0] == 0:
+            return (torch.full((m,), float("inf"), dtype=torch.float64, device=dev),
+                    torch.full((m,), -1, dtype=torch.int64, device=dev))
+        ref = NearestTable(ref)
+    return ref.query(queries, max_dist)
+
+
+def _icp_args(source, target, index):
+    _chk_points(source, "source")
+    _chk_points(target, "target")
+    _chk(index, torch.int64, "index")
+    if index.shape != (source.shape[0],):
+        raise ValueError(f"index: expected ({source.shape[0]},), got {tuple(index.shape)}")
+    return torch.empty(FSCORE_ICP_SLOTS * 9, dtype=torch.float64, device=source.device)
+
+
+def fscore_icp_sums(source, target, index, dist):
+    """(8,) float64 device tensor [pairs, sum of source (3), sum of target (3), sum of dist^2] over the pairs (source[i],
+    target[index[i]]), index[i] >= 0.  Fixed-slot partial sums added in slot order: the same bits on every run."""
+    part = _icp_args(source, target, index)
+    _chk(dist, torch.float64, "dist")
+    if dist.shape != index.shape:
+        raise ValueError(f"dist: expected {tuple(index.shape)}, got {tuple(dist.shape)}")
+    out = torch.zeros(8, dtype=torch.float64, device=source.device)
+    if source.shape[0] == 0 or target.shape[0] == 0:
+        return out
+    _lib.lib().surf_fscore_icp_sums(_p(source), _p(target), target.shape[0], _p(index), _p(dist), source.shape[0], _p(part), _p(out),
+                                    _stream())
+    return out
+
+
+def fscore_icp_cov(source, target, index, centroid_source, centroid_target):
+    """(3, 3) float64 device tensor H[r][c] = sum (source[r] - cs[r]) * (target[index][c] - ct[c]) over the same pairs, reduced
+    like fscore_icp_sums; the centroids are host triples."""
+    part = _icp_args(source, target, index)
+    out = torch.zeros(9, dtype=torch.float64, device=source.device)
+    if source.shape[0] == 0 or target.shape[0] == 0:
+        return out.reshape(3, 3)
+    c = np.ascontiguousarray(np.concatenate([np.asarray(centroid_source, dtype=np.float64).reshape(3),
+                                             np.asarray(centroid_target, dtype=np.float64).reshape(3)]))
+    _lib.lib().surf_fscore_icp_cov(_p(source), _p(target), target.shape[0], _p(index), source.shape[0], _np_ptr(c), _p(part), _p(out),
+                                   _stream())
+    return out.reshape(3, 3)
+
+
 # ------------------------------------------------------------------------------------------------
 # mesh cleaning (mesh_clean.hip): dilation, visual hull, visible faces, face components, compaction
 # ------------------------------------------------------------------------------------------------
