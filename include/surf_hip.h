@@ -942,6 +942,28 @@ int surf_fuse_vertex_colors_bricks(const double* vertices, int64_t n_vertices, c
                                    int ny, int nz, uint8_t* out, void* stream);
 
 /*
+ * Ray casting of the fused state (surf_amd/fusion.py FusionVolume.ray_cast; ray_cast.hip): per pixel of an (H,W) image of any camera
+ * the first front-to-inside crossing of tsdf = level along the pixel's ray, found by a cell-by-cell walk of the lattice over the cells
+ * whose eight corners are observed (weight > 0; in the brick layout a corner of an unallocated brick is unobserved) and refined by a
+ * fixed number of evaluations of the cell's trilinear interpolant.  Added under SURF_ABI_VERSION 41 without a bump, like the entry
+ * points above.  The lattice must be uniform; the rule and its fp32 operation order are written out in ray_cast.hip's header comment,
+ * and the two entry points return equal arrays on a dense and a brick-sparse state of the same views.
+ *   HOST h_lift (12) fp32, in lattice-index units: M^-1 / voxel (row-major), then (-M^-1 t - lo) / voxel of the camera P = [M | t]
+ *     (world -> (x z, y z, z)) and the lattice world = lo + voxel * index, formed in float64 and rounded once.
+ *   z_min >= 0: rays start at z-depth z_min.  level = -isovalue in (-1, 1).
+ *   depth (H,W): z-depth in world units of the crossing, 0 where there is none.  normal (H,W,3) or NULL: the normalised gradient of the
+ *     interpolant there, world frame, pointing into free space; 0 where there is no hit.  out_color (H,W,3): the colour state
+ *     interpolated in the same cell; given exactly when color is (SURF_E_ARG otherwise).  Every pixel is written.
+ *   H W == 0 succeeds without a launch.  SURF_E_LIMIT: the limits of surf_fuse_integrate (surf_fuse_ray_cast) or of
+ *     surf_fuse_integrate_bricks (surf_fuse_ray_cast_bricks), an axis, H or W above 2^24, H W >= 2^31.
+ */
+int surf_fuse_ray_cast(const float* tsdf, const float* weight, const float* color, int nx, int ny, int nz, const float* h_lift,
+                       int H, int W, float z_min, float level, float* depth, float* normal, float* out_color, void* stream);
+int surf_fuse_ray_cast_bricks(const float* tsdf, const float* weight, const float* color, const int32_t* table, int64_t n_slots,
+                              int nx, int ny, int nz, const float* h_lift, int H, int W, float z_min, float level, float* depth,
+                              float* normal, float* out_color, void* stream);
+
+/*
  * Multi-view geometric consistency of depth maps (surf_amd/fusion.py filter_views; depth_filter.hip): which pixels of a reference
  * depth map do enough other views agree with?  A pixel is lifted with its depth, projected into a source view, the source's depth
  * is read there (bilinear over four MEASURED taps), the source point is projected back, and the source agrees when the round trip

@@ -26,6 +26,12 @@ With --scene NAME instead of --scan N the conf's own dataset (e.g. TanksDataset)
 after it (<NAME>.ply, <NAME>_points.ply, fused_<NAME>.json; the record carries `scene`); --tnt_dir D [--tau X] [--no_refine] then
 scores the mesh (and the cloud) with the Tanks and Temples protocol (evaluation.fscore.evaluate_scene): precision, recall, fscore
 (pcd_* for the cloud) and ms.evaluate_fscore.  --clean_mesh and --eval_dir are DTU's protocol and stay with --scan.
+With --render_views [DIR] the fused model is then ray-cast (FusionVolume.ray_cast, csrc/ray_cast.hip: no mesh involved) from every
+fused reference view's camera at its depth map's size: DIR (default <out>/renders/<name>) gets <view>_depth.pfm (z-depth in world
+units, 0 = no hit), <view>_normal.png and, with --colors, <view>_color.png; the record gains `model_residual` - per view and pooled
+over them, the share of the view's measured pixels the model also hits and the median / 90th percentile of |view depth - model
+depth| over those, in world units and in lattice steps (fusion.view_residual: a quality number that needs no ground truth) - and
+`render_views_ms`.  Without the switch the record and the files are what they were.
 Measurement harness like scripts/dtu_chamfer.py: one scan per call, no logging framework, no resume logic."""
 import argparse
 import json
@@ -87,6 +93,10 @@ def parse_args(argv=None):
                          "F-score of the mesh (and of the cloud with --point_cloud), evaluation/fscore.py; needs --scene")
     ap.add_argument("--tau", type=float, default=None, help="F-score distance threshold (default: the benchmark's value for the scene)")
     ap.add_argument("--no_refine", action="store_true", help="F-score: use <scene>_trans.txt as it is, no ICP")
+    ap.add_argument("--render_views", nargs="?", const="", default=None, metavar="DIR",
+                    help="after fusing, ray-cast the model from every fused reference view's camera (FusionVolume.ray_cast): depth "
+                         "(.pfm), normal and colour (.png) maps into DIR (default <out_dir>/renders/<name>), and `model_residual` in "
+                         "the record")
     ap.add_argument("--out_dir", default="./outputs")
     ap.add_argument("--sdf_precision", default=None, choices=["f32", "bf16x3", "f16x2"])
     ap.add_argument("--logit_override", default=None, choices=["sphere"],
@@ -107,6 +117,7 @@ def run(args, state=None):
     dev = torch.device(args.device)
     # a caller may build the Namespace by hand without the scene / F-score attributes
     scene, tnt_dir = getattr(args, "scene", None), getattr(args, "tnt_dir", None)
+    render_dir = getattr(args, "render_views", None)
     name = scene if scene is not None else f"scan{args.scan}"
     if scene is not None and (args.clean_mesh or args.eval_dir is not None):
         raise SystemExit("fuse_scene: --clean_mesh and --eval_dir are DTU's protocol and need --scan, not --scene")
@@ -157,6 +168,7 @@ def run(args, state=None):
     # ---- one forward per reference view; views are integrated 16 per launch ----
     ms.update(forward=0.0, integrate=0.0)
     pending, cloud_views = [], []
+    render_views, render_names = [], []                # --render_views: the views as they are fused, and what their files are called
 
     def flush():
         t0 = time.perf_counter()
@@ -175,6 +187,10 @@ def run(args, state=None):
         pending.append(fusion.view_from_val(item, out, depth=args.depth))
         if args.point_cloud:
             cloud_views.append(pending[-1])
+        if render_dir is not None:
+            render_views.append(pending[-1])
+            ids = item.get("view_ids")
+            render_names.append(f"{name}_{len(render_names):03d}" if ids is None else f"{name}_view{int(ids.reshape(-1)[0]):03d}")
         del out, inputs
         ms["forward"] += 1e3 * (time.perf_counter() - t0)
         if len(pending) == 16 and args.min_consistent == 0:
@@ -201,6 +217,8 @@ def run(args, state=None):
         sync()
         ms["filter"] = 1e3 * (time.perf_counter() - t0)
         pending.clear()
+        if render_dir is not None:
+            render_views = list(views)                 # the residual is taken against the depths that were fused
         for s in range(0, len(views), 16):
             pending.extend(views[s:s + 16])
             flush()
@@ -233,11 +251,37 @@ def run(args, state=None):
         state.update(model=model, volume=volume, vertices=v, triangles=t, colors=colors)
         if cloud is not None:
             state.update(cloud=cloud)
+    model_residual = None
+    if render_dir is not None:
+        # ---- the fused model seen from every fused view's camera: no mesh involved, one kernel launch and one copy per view ----
+        from PIL import Image
+        from surf_amd.datasets import mvs_io
+        t0 = time.perf_counter()
+        render_dir = render_dir or os.path.join(args.out_dir, "renders", name)
+        os.makedirs(render_dir, exist_ok=True)
+        per_view, residuals = [], []
+        for vname, view in zip(render_names, render_views):
+            cast = volume.ray_cast(view.P, tuple(view.depth.shape))
+            mvs_io.write_pfm(os.path.join(render_dir, f"{vname}_depth.pfm"), cast["depth"])
+            Image.fromarray(fusion.quantise_colors_host(0.5 * cast["normal"] + 0.5 * (cast["depth"] > 0)[..., None])).save(
+                os.path.join(render_dir, f"{vname}_normal.png"))
+            if cast["color"] is not None:
+                Image.fromarray(fusion.quantise_colors_host(cast["color"])).save(os.path.join(render_dir, f"{vname}_color.png"))
+            res = fusion.view_residual(view, cast)
+            residuals.append(res.pop("residuals"))
+            per_view.append({"view": vname, **res})
+        measured, hit = sum(r["measured"] for r in per_view), sum(r["hit"] for r in per_view)
+        pooled = {"measured": measured, "hit": hit, "hit_share": hit / max(measured, 1)}
+        pooled.update(fusion.pooled_residual(np.concatenate(residuals) if residuals else np.zeros(0), volume.lattice()[1]))
+        model_residual = {"views": per_view, "pooled": pooled, "dir": render_dir}
+        render_ms = 1e3 * (time.perf_counter() - t0)
     rec = {("scan" if scene is None else "scene"): (args.scan if scene is None else scene), "views_fused": volume.n_views, "lattice": list(volume.shape), "voxel": voxel, "trunc": volume.trunc,
            "observed_share": volume.observed_share(), "vertices": int(len(v)), "triangles": int(len(t)), "depth": args.depth,
            "colors": bool(args.colors), "cleaned": bool(args.clean_mesh), "mesh": mesh_path, "ms": ms}
     if args.sparse:                                     # without the flag the record is what it was
         rec.update(sparse=True, bricks=volume.n_bricks, allocated_share=volume.allocated_share(), state_bytes=volume.state_bytes())
+    if model_residual is not None:                      # without the switch the record is what it was
+        rec.update(model_residual=model_residual, render_views_ms=render_ms)
     if filtered is not None:
         rec.update(min_consistent=args.min_consistent, kept_share=sum(filtered["kept"]) / max(sum(filtered["measured"]), 1))
     if cloud is not None:

@@ -29,6 +29,11 @@ numpy-fp32 mirror, equal arrays again).  It needs no object masks, unlike the DT
 The other product of the same depth maps: fuse_points(views, min_consistent) merges the consistent depths into ONE point cloud,
 one point per surface sample (csrc/point_cloud.hip; backend="host" is its numpy-fp32 mirror, equal arrays) - no lattice, no
 quantisation to a voxel size; mesh_io.write_ply_points writes it, evaluation.dtu_eval scores it with mode="pcd".
+
+Looking at the fused model: vol.ray_cast(P, (H, W)) casts one ray per pixel of any camera through the lattice (dense or sparse,
+csrc/ray_cast.hip; backend="host": ray_cast_host, its numpy-fp32 mirror, equal arrays) and returns the z-depth of the first
+front-to-inside crossing - a DepthView depth with dscale 1 - the surface normal and the fused colour there, without a mesh;
+view_residual(view, cast) is how far a view's own depth map lies from the model, a quality number that needs no ground truth.
 """
 from collections import namedtuple
 
@@ -457,6 +462,214 @@ def fuse_points(views, min_consistent, px_thresh=CONSISTENCY_PX, rel_thresh=CONS
     return PointCloud(points, colors, origin)
 
 
+# ---- ray casting of the fused state (csrc/ray_cast.hip): depth, normal and colour of the model from any camera ----
+
+RAY_REFINE_EVALS = 3             # evaluations of the interpolant that refine a root inside its cell (ray_cast.hip's constant)
+
+
+def uniform_lattice(axes):
+    """(lo (3,) float64, voxel) of coordinate arrays that are one uniform lattice lo + voxel * index to fp32 rounding: voxel is the
+    mean step of the longest axis, and every value lies within 2 ulp (of its axis' largest magnitude) of a[0] + voxel * i - one for
+    the rounding of the values themselves, one for the step taken from another axis.  ValueError naming the reason otherwise."""
+    axes = [np.asarray(a, np.float64).reshape(-1) for a in axes]
+    if any(len(a) < 2 for a in axes):
+        raise ValueError("ray_cast: every axis needs two lattice points (a lattice without cells has nothing to cast)")
+    longest = max(axes, key=len)
+    voxel = float(longest[-1] - longest[0]) / (len(longest) - 1)
+    if not voxel > 0:
+        raise ValueError("ray_cast: the lattice axes must increase")
+    for name, a in zip("xyz", axes):
+        tol = 2.0 * float(np.spacing(np.float32(np.abs(a).max())))
+        dev = float(np.abs(a - (a[0] + voxel * np.arange(len(a)))).max())
+        if not dev <= tol:
+            raise ValueError(f"ray_cast needs a uniform lattice: axis {name} departs by {dev:.3g} from a uniform step of {voxel:.6g} "
+                             f"(fp32 rounding allows {tol:.3g})")
+    return np.array([a[0] for a in axes]), voxel
+
+
+def ray_lift(P, lo, voxel):
+    """The 12 fp32 values of ray_cast.hip's camera, in lattice-index units: L (9, row-major) = M^-1 / voxel, then
+    c = (-M^-1 t - lo) / voxel of P = [M | t], formed in float64 and rounded once.  Pixel (x, y) at z-depth z is the lattice-index
+    point c + z L (x, y, 1)."""
+    P = _np(P, np.float64)
+    if P.size != 12:
+        raise ValueError("ray_cast: P (3, 4)")
+    P = P.reshape(3, 4)
+    M_inv = np.linalg.inv(P[:, :3])
+    lo, voxel = np.asarray(lo, np.float64).reshape(3), float(voxel)
+    return np.concatenate([(M_inv / voxel).reshape(9), (-(M_inv @ P[:, 3]) - lo) / voxel]).astype(np.float32)
+
+
+def _lerp(a, b, u):
+    return (np.float32(1.0) - u) * a + u * b
+
+
+def _clamp01(v):
+    return np.minimum(np.maximum(v, np.float32(0.0)), np.float32(1.0))
+
+
+def _trilerp(v, ux, uy, uz):
+    """ray_cast.hip's f: corner index dx * 4 + dy * 2 + dz, lerp over x, then y, then z."""
+    c00, c10, c01, c11 = _lerp(v[0], v[4], ux), _lerp(v[2], v[6], ux), _lerp(v[1], v[5], ux), _lerp(v[3], v[7], ux)
+    return _lerp(_lerp(c00, c10, uy), _lerp(c01, c11, uy), uz)
+
+
+def ray_cast_host(tsdf, weight, color, shape, lift, hw, z_min=0.0, level=0.0, normals=True, table=None):
+    """The rule of ray_cast.hip's header comment in numpy fp32, one operation per operator in its order, vectorised over the rays
+    with a masked loop over the crossings (rays are independent, so this is the kernel's per-ray loop).  Dense state
+    (table None: tsdf / weight (nx, ny, nz), color (nx, ny, nz, 3) or None) or brick-major state (table: the brick table, tsdf /
+    weight (n_slots * 512,), color (n_slots * 512, 3) or None) of the uniform lattice `shape`; lift: ray_lift(); level = -isovalue.
+    Returns (depth (H, W), normal (H, W, 3) or None, color (H, W, 3) or None) fp32."""
+    f32 = np.float32
+    shape = tuple(int(v) for v in shape)
+    nx, ny, nz = shape
+    H, W = (int(v) for v in hw)
+    N = H * W
+    L = np.asarray(lift, f32).reshape(12)
+    level, inf = f32(level), f32(np.inf)
+    tsdf_f, weight_f = np.asarray(tsdf, f32).reshape(-1), np.asarray(weight, f32).reshape(-1)
+    color_f = None if color is None else np.asarray(color, f32).reshape(-1, 3)
+    out_d, out_n, out_c = np.zeros(N, f32), np.zeros((N, 3), f32), np.zeros((N, 3), f32)
+
+    def result():
+        return (out_d.reshape(H, W), out_n.reshape(H, W, 3) if normals else None, None if color is None else out_c.reshape(H, W, 3))
+
+    if N == 0 or min(shape) < 2 or tsdf_f.size == 0:
+        return result()
+    if table is not None:
+        table = np.asarray(table).reshape(-1)
+        nbp = (max(shape) + 7) // 8
+
+    def corners(ic):
+        """(positions of the eight corners in the flat state, all allocated)"""
+        pos, ok = [], np.ones(len(ic[0]), bool)
+        for k in range(8):
+            x, y, z = ic[0] + (k >> 2), ic[1] + ((k >> 1) & 1), ic[2] + (k & 1)
+            if table is None:
+                pos.append((x * ny + y) * nz + z)
+            else:
+                s = table[((x >> 3) * nbp + (y >> 3)) * nbp + (z >> 3)].astype(np.int64)
+                ok &= s >= 0
+                pos.append(np.maximum(s, 0) * 512 + (((x & 7) << 6) | ((y & 7) << 3) | (z & 7)))
+        return pos, ok
+
+    yy, xx = np.mgrid[:H, :W]
+    xf, yf = xx.reshape(-1).astype(f32), yy.reshape(-1).astype(f32)
+    with np.errstate(all="ignore"):
+        r = [(L[3 * a] * xf + L[3 * a + 1] * yf) + L[3 * a + 2] for a in range(3)]
+        c = [L[9 + a] for a in range(3)]
+        m = [f32(shape[a] - 1) for a in range(3)]
+        # ---- clip to the box of cells and to z > z_min ----
+        te, tx, live = np.full(N, f32(z_min)), np.full(N, inf), np.ones(N, bool)
+        for a in range(3):
+            moves = r[a] != 0
+            t0, t1 = (f32(0.0) - c[a]) / r[a], (m[a] - c[a]) / r[a]
+            nr, fr = np.where(t0 < t1, t0, t1), np.where(t0 < t1, t1, t0)
+            te = np.where(moves & (nr > te), nr, te)
+            tx = np.where(moves & (fr < tx), fr, tx)
+            live &= moves | ((c[a] >= 0) & (c[a] <= m[a]))
+        live &= te < tx
+        idx = np.flatnonzero(live)                         # the rays still walking, and their state
+        r = [ra[idx] for ra in r]
+        t_in = te[idx]
+        ic, u = [], []
+        for a in range(3):
+            p = c[a] + t_in * r[a]
+            fl = np.minimum(np.maximum(np.floor(p), f32(0.0)), m[a] - f32(1.0))
+            ic.append(fl.astype(np.int64))
+            u.append(_clamp01(p - fl))
+        for _ in range(nx + ny + nz):
+            if len(idx) == 0:
+                break
+            # ---- the crossing that ends this cell, from the integer plane indices ----
+            tc = [np.where(r[a] != 0, (np.where(r[a] > 0, ic[a] + 1, ic[a]).astype(f32) - c[a]) / r[a], inf) for a in range(3)]
+            axis, to = np.zeros(len(idx), np.int64), tc[0]
+            for a in (1, 2):
+                sooner = tc[a] < to
+                axis, to = np.where(sooner, a, axis), np.where(sooner, tc[a], to)
+            keep = np.abs(to) <= _F32_MAX                  # no finite crossing: the walk ends
+            if not keep.all():
+                idx, t_in, axis, to = idx[keep], t_in[keep], axis[keep], to[keep]
+                r, ic, u = [v[keep] for v in r], [v[keep] for v in ic], [v[keep] for v in u]
+            w, step = [], []
+            for a in range(3):
+                p = c[a] + to * r[a]
+                w.append(np.where(axis == a, np.where(r[a] > 0, f32(1.0), f32(0.0)), _clamp01(p - ic[a].astype(f32))))
+                step.append(np.where(axis == a, np.where(r[a] > 0, 1, -1), 0))
+            # ---- does the cell count?  all eight corners observed ----
+            pos, counted = corners(ic)
+            for k in range(8):
+                counted &= weight_f[pos[k]] > 0
+            v = [tsdf_f[pos[k]] - level for k in range(8)]
+            f_in, f_out = _trilerp(v, *u), _trilerp(v, *w)
+            hit = counted & (f_in > 0) & (f_out <= 0)
+            if hit.any():
+                h = np.flatnonzero(hit)
+                ta, fa, tb, fb = t_in[h], f_in[h], to[h], f_out[h]
+                vh, rh, fi = [vk[h] for vk in v], [ra[h] for ra in r], [ia[h].astype(f32) for ia in ic]
+
+                def local(t):
+                    return [_clamp01((c[a] + t * rh[a]) - fi[a]) for a in range(3)]
+                for _e in range(RAY_REFINE_EVALS):
+                    t = ta + (tb - ta) * (fa / (fa - fb))
+                    g = _trilerp(vh, *local(t))
+                    front = g > 0
+                    ta, fa, tb, fb = np.where(front, t, ta), np.where(front, g, fa), np.where(front, tb, t), np.where(front, fb, g)
+                z = ta + (tb - ta) * (fa / (fa - fb))
+                ux, uy, uz = local(z)
+                out_d[idx[h]] = z
+                gx = _lerp(_lerp(vh[4] - vh[0], vh[6] - vh[2], uy), _lerp(vh[5] - vh[1], vh[7] - vh[3], uy), uz)
+                gy = _lerp(_lerp(vh[2] - vh[0], vh[6] - vh[4], ux), _lerp(vh[3] - vh[1], vh[7] - vh[5], ux), uz)
+                gz = _lerp(_lerp(vh[1] - vh[0], vh[5] - vh[4], ux), _lerp(vh[3] - vh[2], vh[7] - vh[6], ux), uy)
+                length = np.sqrt((gx * gx + gy * gy) + gz * gz)
+                out_n[idx[h]] = np.where((length > 0)[:, None], np.stack([gx / length, gy / length, gz / length], axis=-1), f32(0.0))
+                if color_f is not None:
+                    cv = [color_f[pos[k][h]] for k in range(8)]
+                    out_c[idx[h]] = _trilerp(cv, ux[:, None], uy[:, None], uz[:, None])
+            # ---- step through the crossed face ----
+            keep = ~hit
+            for a in range(3):
+                ic[a] = ic[a] + step[a]
+                keep &= (ic[a] >= 0) & (ic[a] <= shape[a] - 2)
+                u[a] = np.where(axis == a, f32(1.0) - w[a], w[a])
+            idx, t_in = idx[keep], to[keep]
+            r, ic, u = [v_[keep] for v_ in r], [v_[keep] for v_ in ic], [v_[keep] for v_ in u]
+    return result()
+
+
+def view_residual(view, cast, voxel=None):
+    """How far a view's own depth map lies from the fused model seen from the same camera.  cast: FusionVolume.ray_cast(view.P,
+    view.depth.shape) (or its depth array, then with voxel=).  Over the view's measured pixels: "measured" (their number), "hit"
+    (those the model also hits), "hit_share" = hit / measured, and over the hit ones the median and 90th percentile of
+    |d_view * dscale - d_model| in world units ("median", "p90") and in lattice steps ("median_voxels", "p90_voxels"; None without a
+    voxel size); "residuals": the world-unit values themselves (fp64), for pooling over views.  No hit pixel: the four are None."""
+    model = cast["depth"] if isinstance(cast, dict) else cast
+    if voxel is None and isinstance(cast, dict):
+        voxel = cast.get("voxel")
+    model = _np(model, np.float64)
+    with np.errstate(all="ignore"):
+        d = (_np(view.depth, np.float32) * np.float32(view.dscale)).astype(np.float64)
+    if model.shape != d.shape:
+        raise ValueError("view_residual: the cast has the size of the view's depth map")
+    measured = (d > 0) & (d <= float(_F32_MAX))
+    both = measured & (model > 0)
+    res = np.abs(d[both] - model[both])
+    out = {"measured": int(measured.sum()), "hit": int(both.sum()), "hit_share": float(both.sum()) / max(int(measured.sum()), 1),
+           "residuals": res}
+    out.update(pooled_residual(res, voxel))
+    return out
+
+
+def pooled_residual(residuals, voxel=None):
+    """median / p90 (world units) and median_voxels / p90_voxels of world-unit residuals (view_residual's, or several views'
+    concatenated)."""
+    if len(residuals) == 0:
+        return {"median": None, "p90": None, "median_voxels": None, "p90_voxels": None}
+    med, p90 = float(np.median(residuals)), float(np.percentile(residuals, 90))
+    return {"median": med, "p90": p90, "median_voxels": None if voxel is None else med / float(voxel),
+            "p90_voxels": None if voxel is None else p90 / float(voxel)}
+
+
 class FusionVolume:
     """A dense world-frame TSDF lattice that depth views are integrated into.
 
@@ -498,6 +711,7 @@ class FusionVolume:
             raise ValueError("FusionVolume: trunc > 0")
         self.backend, self.shape, self.n_views = backend, tuple(len(a) for a in axes), 0
         self.axes_host = axes
+        self._by_voxel = (np.asarray(grid[0], np.float64).reshape(3), float(grid[2])) if by_voxel else None     # ray_cast's (lo, voxel)
         if backend == "device":
             if not torch.cuda.is_available():
                 raise RuntimeError("FusionVolume(backend='device') needs a GPU (the SuRF hot path has no CPU fallback)")
@@ -549,6 +763,65 @@ class FusionVolume:
             axes = [torch.from_numpy(a).to(dev) for a in self.axes]
         v, t = ops.marching_cubes(ops.fuse_lattice(tsdf, weight), float(isovalue), observed_only=True)
         return self._mesh_to_host(v, t, None if color is None else ops.fuse_vertex_colors(v, color), axes)
+
+    def lattice(self):
+        """(lo (3,) float64, voxel) of a uniform lattice: the (lo, hi, voxel) it was built from, or what its coordinate arrays
+        follow to fp32 rounding (uniform_lattice; ValueError naming the reason otherwise)."""
+        if self._by_voxel is not None and min(self.shape) >= 2:
+            return self._by_voxel
+        return uniform_lattice(self.axes_host)
+
+    def _ray_state(self):
+        """(tsdf, weight, color, table or None, lattice has state at all) for ray_cast."""
+        return self.tsdf, self.weight, self.color, None, True
+
+    def ray_cast(self, P, hw, z_min=0.0, isovalue=0.0, normals=True, return_tensors=False):
+        """The fused model seen from the camera P (3, 4) (DepthView's: world -> (x z, y z, z)) at an (H, W) image:
+        {"depth": (H, W) fp32 z-depth in world units at the first front-to-inside crossing of u = -tsdf = isovalue over the cells
+        whose eight corners were observed, 0 where the ray meets none - a DepthView depth with dscale 1; "normal": (H, W, 3) unit
+        normals in the world frame pointing into free space (0 without a hit; None with normals=False); "color": (H, W, 3) fp32 in
+        image units when colours are fused, else None; "voxel": the lattice step}.  The rule is written out in csrc/ray_cast.hip's
+        header comment; backend "host" is its numpy-fp32 mirror (equal arrays), and a sparse volume returns the dense volume's
+        arrays.  z_min >= 0: rays start at that z-depth.  Needs a uniform lattice (lattice()).  numpy arrays unless
+        return_tensors (device backend: device tensors, no host copy)."""
+        P = _np(P, np.float64)
+        if P.shape not in ((3, 4), (12,)) or not np.isfinite(P).all():
+            raise ValueError("FusionVolume.ray_cast: P is a finite (3, 4) matrix")
+        try:
+            H, W = (int(v) for v in hw)
+            ok = len(hw) == 2 and H >= 1 and W >= 1 and all(int(v) == v for v in hw)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError("FusionVolume.ray_cast: hw = (H, W), two positive integers")
+        if not -1.0 < float(isovalue) < 1.0:
+            raise ValueError("FusionVolume.ray_cast: -1 < isovalue < 1")
+        if not (0.0 <= float(z_min) <= float(_F32_MAX)):
+            raise ValueError("FusionVolume.ray_cast: z_min >= 0")
+        lo, voxel = self.lattice()
+        P = P.reshape(3, 4)
+        if not abs(np.linalg.det(P[:, :3])) > 0:
+            raise ValueError("FusionVolume.ray_cast: P = [M | t] with an invertible M")
+        lift, level = ray_lift(P, lo, voxel), -float(isovalue)
+        tsdf, weight, color, table, any_state = self._ray_state()
+        if self.backend == "device":
+            if not any_state:
+                d, n, c = (torch.zeros((H, W) + tail, dtype=torch.float32, device=self.device) for tail in ((), (3,), (3,)))
+                d, n, c = d, (n if normals else None), (c if self.color is not None else None)
+            elif table is None:
+                d, n, c = ops.fuse_ray_cast(tsdf, weight, color, lift, (H, W), z_min, level, normals)
+            else:
+                d, n, c = ops.fuse_ray_cast_bricks(tsdf, weight, color, table, self.shape, lift, (H, W), z_min, level, normals)
+            if not return_tensors:
+                flat = to_host(torch.cat([x.reshape(-1) for x in (d, n, c) if x is not None])).numpy()
+                parts = np.split(flat, np.cumsum([x.numel() for x in (d, n, c) if x is not None])[:-1])
+                it = iter(parts)
+                d, n, c = (None if x is None else next(it).reshape(tuple(x.shape)) for x in (d, n, c))
+        else:
+            d, n, c = ray_cast_host(tsdf, weight, color, self.shape, lift, (H, W), z_min, level, normals, table=table)
+            if return_tensors:
+                d, n, c = (None if x is None else torch.from_numpy(x) for x in (d, n, c))
+        return {"depth": d, "normal": n, "color": c, "voxel": voxel}
 
     @staticmethod
     def _mesh_to_host(v, t, c, axes):
@@ -739,6 +1012,10 @@ class SparseFusionVolume(FusionVolume):
     def state_bytes(self):
         """Bytes of the built state: tsdf, weight (and colours) of the allocated bricks, the brick list and the brick table."""
         return self.n_bricks * (512 * (20 if self.colors else 8) + 4) + 4 * self.nbp ** 3
+
+    def _ray_state(self):
+        bricks, table, tsdf, weight, color = self.finalize()._state
+        return tsdf, weight, color, table, self.n_bricks > 0
 
     def extract_mesh(self, isovalue=0.0):
         """FusionVolume.extract_mesh's arrays, the same mesh in the same order, for -1 < isovalue < 1 (ValueError otherwise: the

@@ -2193,6 +2193,64 @@ def fuse_vertex_colors_bricks(vertices, color, table, shape):
     return out
 
 
+# ---- ray casting of the fused state (ray_cast.hip): depth, normal and colour of the model from any camera ----
+
+def _ray_cast_outputs(hw, color, normals, dev):
+    H, W = (int(v) for v in hw)
+    if H < 0 or W < 0:
+        raise ValueError("fuse_ray_cast: hw = (H, W), both >= 0")
+    depth = torch.empty(H, W, dtype=torch.float32, device=dev)
+    normal = torch.empty(H, W, 3, dtype=torch.float32, device=dev) if normals else None
+    out_color = None if color is None else torch.empty(H, W, 3, dtype=torch.float32, device=dev)
+    return H, W, depth, normal, out_color
+
+
+def fuse_ray_cast(tsdf, weight, color, lift, hw, z_min=0.0, level=0.0, normals=True):
+    """The dense state tsdf / weight (nx, ny, nz) (and color (nx, ny, nz, 3) or None) of a UNIFORM lattice seen from one camera:
+    (depth (H, W), normal (H, W, 3) or None, color (H, W, 3) or None) fp32 device tensors.  lift: fusion.ray_lift(P, lo, voxel)
+    (12 fp32 on the host, lattice-index units); level = -isovalue.  The rule is written out in ray_cast.hip's header comment."""
+    _chk(tsdf, torch.float32, "tsdf")
+    _chk(weight, torch.float32, "weight")
+    if tsdf.dim() != 3 or weight.shape != tsdf.shape:
+        raise ValueError("fuse_ray_cast: tsdf and weight (nx, ny, nz)")
+    if color is not None:
+        _chk(color, torch.float32, "color")
+        if tuple(color.shape) != tuple(tsdf.shape) + (3,):
+            raise ValueError("fuse_ray_cast: color (nx, ny, nz, 3)")
+    lift = np.ascontiguousarray(np.asarray(lift, dtype=np.float32).reshape(12))
+    H, W, depth, normal, out_color = _ray_cast_outputs(hw, color, normals, tsdf.device)
+    nx, ny, nz = (int(v) for v in tsdf.shape)
+    _lib.lib().surf_fuse_ray_cast(_p(tsdf), _p(weight), _p(color), nx, ny, nz, _np_ptr(lift), H, W, ctypes.c_float(float(z_min)),
+                                  ctypes.c_float(float(level)), _p(depth), _p(normal), _p(out_color), _stream())
+    return depth, normal, out_color
+
+
+def fuse_ray_cast_bricks(tsdf, weight, color, table, shape, lift, hw, z_min=0.0, level=0.0, normals=True):
+    """fuse_ray_cast on brick-major state (tsdf / weight (n_slots * 512,), color (n_slots * 512, 3) or None) of the lattice `shape`,
+    read through the brick table: a corner in a brick that is not allocated is unobserved.  Equal arrays."""
+    _chk(tsdf, torch.float32, "tsdf")
+    _chk(weight, torch.float32, "weight")
+    _chk(table, torch.int32, "table")
+    m = tsdf.numel() // 512
+    if tsdf.numel() != m * 512 or weight.numel() != m * 512:
+        raise ValueError("fuse_ray_cast_bricks: tsdf and weight hold 512 points per brick")
+    if color is not None:
+        _chk(color, torch.float32, "color")
+        if color.numel() != m * 512 * 3:
+            raise ValueError("fuse_ray_cast_bricks: color holds 512 x 3 values per brick")
+    nx, ny, nz = (int(v) for v in shape)
+    if table.numel() != fuse_brick_dims(shape)[1] ** 3:
+        raise ValueError("fuse_ray_cast_bricks: table holds one entry per brick")
+    lift = np.ascontiguousarray(np.asarray(lift, dtype=np.float32).reshape(12))
+    H, W, depth, normal, out_color = _ray_cast_outputs(hw, color, normals, table.device)
+    if m == 0:                                                     # nothing allocated: nothing is observed, no ray hits
+        return depth.zero_(), None if normal is None else normal.zero_(), None if out_color is None else out_color.zero_()
+    _lib.lib().surf_fuse_ray_cast_bricks(_p(tsdf), _p(weight), _p(color), _p(table), m, nx, ny, nz, _np_ptr(lift), H, W,
+                                         ctypes.c_float(float(z_min)), ctypes.c_float(float(level)), _p(depth), _p(normal),
+                                         _p(out_color), _stream())
+    return depth, normal, out_color
+
+
 # ------------------------------------------------------------------------------------------------
 # multi-view geometric consistency of depth maps (depth_filter.hip): which pixels do enough other views agree with
 # ------------------------------------------------------------------------------------------------
