@@ -1064,6 +1064,82 @@ int surf_fscore_icp_sums(const double* source, const double* target, int64_t n_t
 int surf_fscore_icp_cov(const double* source, const double* target, int64_t n_target, const int64_t* index, int64_t n,
                         const double* h_centroids, double* partials, double* out, void* stream);
 
+/*
+ * Mesh simplification by vertex clustering with quadric placement (surf_amd/mesh_simplify.py, backend="device";
+ * mesh_simplify.hip).  Added under SURF_ABI_VERSION 41 without a bump, like the entry points above.  The device path returns the
+ * host path's arrays: both follow the rule below, fp64 with separate multiplies and adds (-ffp-contract=off), every sum of more
+ * than two terms parenthesised from the left.
+ *
+ * THE RULE.  vertices (n,3) fp32, faces (m,3) int32, optional normals (n,3) fp32 and colors (n,3) uint8, cell > 0 (fp64).
+ *   1. cell of a vertex: i[a] = floor(double(v[a]) / cell); the lattice is anchored at the world origin.  key = ((ix + 2^20) << 42)
+ *      | ((iy + 2^20) << 21) | (iz + 2^20).  A non-finite coordinate or an index outside [-2^20, 2^20) is SURF_E_LIMIT.
+ *      centre[a] = (double(i[a]) + 0.5) * cell.
+ *   2. per face (p = double(v[faces[f]])): e1 = p1 - p0, e2 = p2 - p0, c = (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z, e1x*e2y - e1y*e2x),
+ *      L = sqrt((cx*cx + cy*cy) + cz*cz).  A face with L == 0, a non-finite L or a repeated index contributes nothing.  Otherwise
+ *      nrm = c / L, w = (L / 2) / (cell*cell), and for each corner k with the centre of ITS vertex's cell: q = (p0 - centre) / cell,
+ *      d = (nx*qx + ny*qy) + nz*qz, g = w * nrm, and the cell receives  A00 += gx*nx  A01 += gx*ny  A02 += gx*nz  A11 += gy*ny
+ *      A12 += gy*nz  A22 += gz*nz  b[a] += (w*d) * nrm[a].  A face inside one cell is added three times.
+ *   3. per vertex, referenced or not, to its cell: count += 1, u[a] += (double(v[a]) - centre[a]) / cell, colour sums (integers),
+ *      normal sums (fp64 of the fp32 values).
+ *   4. accumulation: SEQUENTIAL, the order is part of the rule (the int64 fixed-point alternative was not taken).  Inside a cell the
+ *      face terms are added in (face index, corner) order and the vertex terms in vertex-index order, each sum starting from +0:
+ *      the caller sorts the corners / the vertices by cell with a STABLE sort and one thread walks a cell's two segments, as
+ *      surf_fscore_voxel_mean does.  np.add.at walks the same order on the host.  No float atomics.
+ *   5. representative: t = (A00 + A11) + A22, mean[a] = u[a] / double(count), s = 2^-20 * t.  If not t > 0: x = mean.  Otherwise
+ *      (A + s I) x = b + s mean by LDL^T without pivoting (the matrix is symmetric positive definite, pivots >= s), written out:
+ *        m00 = A00 + s   m11 = A11 + s   m22 = A22 + s   r[a] = b[a] + s * mean[a]
+ *        l10 = A01 / m00          l20 = A02 / m00
+ *        d1  = m11 - l10 * A01    u21 = A12 - l20 * A01    l21 = u21 / d1    d2 = (m22 - l20 * A02) - l21 * u21
+ *        y1  = r1 - l10 * r0      y2  = (r2 - l20 * r0) - l21 * y1
+ *        x2  = y2 / d2            x1  = y1 / d1 - l21 * x2                   x0 = (r0 / m00 - l10 * x1) - l20 * x2
+ *      then x[a] = min(max(x[a], -0.5), 0.5) and position[a] = float(centre[a] + x[a] * cell).
+ *   6. colour = (2 sum + count) / (2 count) in integers (rounded to nearest, halves up).  normal = float(S[a] / len) with
+ *      len = sqrt((Sx*Sx + Sy*Sy) + Sz*Sz), or (0,0,0) when len is 0 or not finite.
+ *   7. faces: every index is replaced by its vertex's cell.  A face with fewer than three distinct cells is dropped.  Of the faces
+ *      with the same set of three cells, in any orientation, the one of lowest input index is kept.  Kept faces stay in input order
+ *      with their own orientation.
+ *   8. output vertices: the cells that a kept face references, numbered in ascending key.  vertex_map (n) int32 = the output index
+ *      of every input vertex's cell, or -1.
+ *
+ * Entry points, in the order surf_amd.ops.simplify_mesh calls them (sorts, scans and searches between them are the caller's):
+ *   surf_simplify_keys: keys (n) int64 of rule 1.  A vertex that breaks rule 1's limit gets key 0 and sets flag[0] = 1 (int32 on the
+ *     device, zeroed by the caller): a launch cannot return it, so the CALLER reads the flag before it goes on and reports
+ *     SURF_E_LIMIT.  !(cell > 0), or a cell whose square is 0 or not finite, is SURF_E_ARG.
+ *   surf_simplify_segments: from sorted_keys / order (n) int64 (the keys' stable ascending sort and its permutation) and rank (n)
+ *     int64 (rank[j] = number of distinct keys among sorted_keys[0..j], minus 1): vertex_cell[order[j]] = rank[j] (n) int32 and
+ *     segment_start (n_cells + 1) int64, the first position of every cell in order, segment_start[n_cells] = n.
+ *   surf_simplify_face_cells: face_cells (m,3) int32 = vertex_cell[faces]; a face with an index outside [0, n) gets (0,0,0) (it is
+ *     dropped by rule 7 and skipped by rule 2) and sets flag[0] = 1.
+ *   surf_simplify_faces: rule 7.  keep (m) uint8.  owner (slots) int32 and face_slot (m) uint32 are scratch; slots is the smallest
+ *     power of two >= max(1024, 2 m) (SURF_E_ARG otherwise).  One table slot per set of cells (open addressing, linear probing; a
+ *     slot is claimed by atomicCAS with a face id and compared through that face's cells), one atomicMin of the face id per face.
+ *   surf_simplify_mark_used: used (n_cells) uint8, zeroed by the caller, = 1 for the cells of the kept faces.
+ *   surf_simplify_cells: rules 2-6, one thread per cell; a used cell c writes row cell_scan[c] - 1 of out_vertices (fp32),
+ *     out_normals (fp32, with normals) and out_colors (uint8, with colors).  corner_order (3 m) int64 = the stable ascending sort
+ *     permutation of face_cells read as a flat array, corner_start (n_cells + 1) int64 the first position of every cell in it;
+ *     vertex_order / vertex_start = order / segment_start above; cell_scan (n_cells) int64 = the INCLUSIVE scan of used.
+ *   surf_simplify_compact: out_faces (kept faces, 3) int32 with row face_scan[f] - 1 = cell_scan[face_cells[f]] - 1 for the kept
+ *     faces (face_scan the INCLUSIVE scan of keep), and vertex_map (n) int32 of rule 8.
+ * n == 0 or m == 0 returns 0 at once where there is nothing to do; n, m >= 2^31 / 3 is SURF_E_LIMIT.
+ */
+int surf_simplify_keys(const float* vertices, int64_t n, double cell, int64_t* keys, int32_t* flag, void* stream);
+int surf_simplify_segments(const int64_t* sorted_keys, const int64_t* order, const int64_t* rank, int64_t n, int64_t n_cells,
+                           int32_t* vertex_cell, int64_t* segment_start, void* stream);
+int surf_simplify_face_cells(const int32_t* faces, int64_t m, const int32_t* vertex_cell, int64_t n, int32_t* face_cells,
+                             int32_t* flag, void* stream);
+int surf_simplify_faces(const int32_t* face_cells, int64_t m, int32_t* owner, int64_t slots, uint32_t* face_slot, uint8_t* keep,
+                        void* stream);
+int surf_simplify_mark_used(const int32_t* face_cells, const uint8_t* keep, int64_t m, int64_t n_cells, uint8_t* used,
+                            void* stream);
+int surf_simplify_cells(const float* vertices, const float* normals, const uint8_t* colors, int64_t n, const int32_t* faces,
+                        int64_t m, double cell, const int64_t* sorted_keys, const int64_t* vertex_order,
+                        const int64_t* vertex_start, const int64_t* corner_order, const int64_t* corner_start, int64_t n_cells,
+                        const uint8_t* used, const int64_t* cell_scan, float* out_vertices, float* out_normals,
+                        uint8_t* out_colors, void* stream);
+int surf_simplify_compact(const int32_t* face_cells, const uint8_t* keep, const int64_t* face_scan, int64_t m,
+                          const int32_t* vertex_cell, int64_t n, const uint8_t* used, const int64_t* cell_scan, int64_t n_cells,
+                          int32_t* out_faces, int32_t* vertex_map, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

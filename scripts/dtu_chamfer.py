@@ -70,6 +70,10 @@ def parse_args(argv=None):
     ap.add_argument("--vertex_colors", action="store_true",
                     help="also write per-vertex normals (nx ny nz) and blended colours (red green blue) into the PLY "
                          "(ImplicitSurface.vertex_attributes on the final vertex set; geometry and Chamfer unchanged)")
+    ap.add_argument("--simplify_cell", type=float, default=None,
+                    help="simplify the mesh to one vertex per cell of this size, in the mesh's own units (the normalised frame the "
+                         "val forward extracts it in), by quadric vertex clustering: the last mesh step, after --clean_mesh")
+    ap.add_argument("--simplify_backend", default="host", choices=["host", "device"])
     ap.add_argument("--downsample_density", type=float, default=0.2)
     ap.add_argument("--patch_size", type=float, default=60)
     ap.add_argument("--max_dist", type=float, default=20)
@@ -91,6 +95,7 @@ def run(args, state=None):
     from surf_amd.datasets import get_loader
     from surf_amd.evaluation import clean_dtu
     from surf_amd.evaluation import clean_mesh as CM
+    from surf_amd.mesh_simplify import simplify_step
     from surf_amd.evaluation import dtu_eval
     from surf_amd.surf import SuRF
 
@@ -158,7 +163,7 @@ def run(args, state=None):
         os.makedirs(os.path.dirname(mesh_path), exist_ok=True)
         if state is not None:
             state.update(model=model, item=item, vertices=v, triangles=t)
-        attrs, t_attr = {}, None
+        attrs, t_attr, simplified = {}, None, None
         if args.vertex_colors:                   # on the final vertex set: after clean_mesh, before scale_mat
             t0 = time.perf_counter()
             attrs = model.vertex_attributes(v)
@@ -171,16 +176,25 @@ def run(args, state=None):
                                                    backend=args.clean_backend, device=dev.type, return_index=True)
             t_clean = time.perf_counter() - t0
             v = np.asarray(v)[kept]
+            normals, colors = attrs.get("normals"), attrs.get("colors")
+            normals, colors = (None if normals is None else normals[kept]), (None if colors is None else colors[kept])
+            if args.simplify_cell is not None:   # the last mesh step, in the normalised frame; the world-frame vertices follow it
+                v, t, normals, colors, simplified = simplify_step(v, t, args.simplify_cell, normals, colors, args.simplify_backend, dev)
+                vw = mesh_io.transform_vertices(v, scale_mat)
             if state is not None:
                 state.update(vertices=v, triangles=t)
-            normals = attrs.get("normals")
             if normals is not None:
-                normals = mesh_io.transform_normals(normals[kept], scale_mat)
-            colors = attrs.get("colors")
-            mesh_io.write_ply(mesh_path, vw, t, normals=normals, colors=None if colors is None else colors[kept])
+                normals = mesh_io.transform_normals(normals, scale_mat)
+            mesh_io.write_ply(mesh_path, vw, t, normals=normals, colors=colors)
         else:
-            mesh_io.export_mesh(mesh_path, v, t, item["scale_mat"], normals=attrs.get("normals"),
-                                colors=attrs.get("colors"))                                       # runner.py:236-240
+            normals, colors = attrs.get("normals"), attrs.get("colors")
+            if args.simplify_cell is not None:
+                v, t, normals, colors, simplified = simplify_step(v, t, args.simplify_cell, normals, colors, args.simplify_backend, dev)
+                if state is not None:
+                    state.update(vertices=v, triangles=t)
+            mesh_io.export_mesh(mesh_path, v, t, item["scale_mat"], normals=normals, colors=colors)   # runner.py:236-240
+        if len(t) == 0:
+            raise SystemExit(f"dtu_chamfer: --simplify_cell {args.simplify_cell} leaves no face (the cell swallows the mesh)")
         t0 = time.perf_counter()
         d2s, s2d, overall = dtu_eval.evaluate_scan(mesh_path, args.eval_dir, args.scan, patch_size=args.patch_size,
                                                    max_dist=args.max_dist, downsample_density=args.downsample_density,
@@ -194,7 +208,8 @@ def run(args, state=None):
                 "checkpoint": args.ckpt, "missing_keys": missing, "unexpected_keys": unexpected, "cleaned": bool(args.clean_mesh),
                 "clean_backend": args.clean_backend if args.clean_mesh else None, "clean_protocol": protocol,
                 "seconds": {"load": t_load, "val_forward": t_val, "clean": t_clean, "evaluate": t_eval,
-                            **({} if t_attr is None else {"vertex_attributes": t_attr})}}
+                            **({} if t_attr is None else {"vertex_attributes": t_attr})},
+                **({} if simplified is None else {"simplify": simplified})}
 
     if not args.sweep:
         rec = evaluate()

@@ -82,6 +82,10 @@ def parse_args(argv=None):
     ap.add_argument("--dtu_test_dir", default=None, help="DTU_TEST tree (cameras/, scan<N>/mask/) of --clean_mesh")
     ap.add_argument("--clean_set", type=int, default=1, choices=[0, 1], help="view set of --clean_mesh")
     ap.add_argument("--clean_backend", default="host", choices=["host", "device"])
+    ap.add_argument("--simplify_mm", type=float, default=None,
+                    help="simplify the mesh to one vertex per cell of this size (world units; DTU: millimetres) by quadric vertex "
+                         "clustering (surf_amd/mesh_simplify.py): the last mesh step, after --clean_mesh, before the PLY and the scores")
+    ap.add_argument("--simplify_backend", default="host", choices=["host", "device"])
     ap.add_argument("--eval_dir", default=None, help="DTU evaluation data (ObsMask/, Points/stl/): also report the Chamfer distance")
     ap.add_argument("--eval_device", default="cpu", choices=["cpu", "gpu"])
     ap.add_argument("--downsample_density", type=float, default=0.2)
@@ -243,6 +247,12 @@ def run(args, state=None):
                                               device=dev.type, return_index=True)
         colors = None if colors is None else colors[kept]
         ms["clean"] = 1e3 * (time.perf_counter() - t0)
+    simplified = None
+    if args.simplify_mm is not None:                    # the last mesh step: the cleaner's component threshold is about the full mesh
+        from surf_amd.mesh_simplify import simplify_step
+        v, t, _, colors, simplified = simplify_step(v, t, args.simplify_mm, colors=colors, backend=args.simplify_backend, device=dev)
+        if len(t) == 0:
+            raise SystemExit(f"fuse_scene: --simplify_mm {args.simplify_mm} leaves no face (the cell swallows the mesh)")
     t0 = time.perf_counter()
     mesh_path = os.path.join(args.out_dir, "meshes", "fused", f"{name}.ply")
     mesh_io.write_ply(mesh_path, v, t, colors=colors)
@@ -280,6 +290,8 @@ def run(args, state=None):
            "colors": bool(args.colors), "cleaned": bool(args.clean_mesh), "mesh": mesh_path, "ms": ms}
     if args.sparse:                                     # without the flag the record is what it was
         rec.update(sparse=True, bricks=volume.n_bricks, allocated_share=volume.allocated_share(), state_bytes=volume.state_bytes())
+    if simplified is not None:                          # without the flag the record is what it was
+        rec.update(simplify=simplified)
     if model_residual is not None:                      # without the switch the record is what it was
         rec.update(model_residual=model_residual, render_views_ms=render_ms)
     if filtered is not None:

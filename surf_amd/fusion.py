@@ -748,10 +748,13 @@ class FusionVolume:
         """Share of the lattice points that at least one view updated."""
         return float((self.weight > 0).sum()) / float(np.prod(self.shape))
 
-    def extract_mesh(self, isovalue=0.0):
+    def extract_mesh(self, isovalue=0.0, simplify_cell=None):
         """(vertices (V, 3) float64 in the world frame, triangles (F, 3) int64[, colors (V, 3) uint8 when colours are fused]) as
         numpy arrays: marching cubes at u = -tsdf = isovalue over the cells whose eight corners were observed, one copy to the
-        host.  Runs on the GPU whatever the backend (the host backend's state is uploaded)."""
+        host.  Runs on the GPU whatever the backend (the host backend's state is uploaded).
+        simplify_cell (world units): the mesh is simplified before it is returned - mesh_simplify.simplify_mesh of exactly the
+        arrays that simplify_cell=None returns, by the volume's backend (on the device the full mesh never visits the host);
+        positions are then fp32 values."""
         if self.backend == "device":
             dev, tsdf, weight, color, axes = self.device, self.tsdf, self.weight, self.color, self.axes
         else:
@@ -762,7 +765,8 @@ class FusionVolume:
             color = None if self.color is None else torch.from_numpy(self.color).to(dev)
             axes = [torch.from_numpy(a).to(dev) for a in self.axes]
         v, t = ops.marching_cubes(ops.fuse_lattice(tsdf, weight), float(isovalue), observed_only=True)
-        return self._mesh_to_host(v, t, None if color is None else ops.fuse_vertex_colors(v, color), axes)
+        c = None if color is None else ops.fuse_vertex_colors(v, color)
+        return self._mesh_to_host(v, t, c, axes) if simplify_cell is None else self._simplified(v, t, c, axes, simplify_cell)
 
     def lattice(self):
         """(lo (3,) float64, voxel) of a uniform lattice: the (lo, hi, voxel) it was built from, or what its coordinate arrays
@@ -824,20 +828,37 @@ class FusionVolume:
         return {"depth": d, "normal": n, "color": c, "voxel": voxel}
 
     @staticmethod
-    def _mesh_to_host(v, t, c, axes):
-        """Device mesh in lattice-index units (+ uint8 vertex colours or None) -> extract_mesh's numpy arrays, one copy."""
-        parts = []
-        if c is not None:
-            c = c.reshape(-1)
-            parts = [torch.cat([c, c.new_zeros((-c.numel()) % 8)]).view(torch.int64)]
-        # lattice-index units -> world: linear along the lattice edge, in float64 (exact for a uniform axis up to its fp32 values)
+    def _world(v, axes):
+        """Device vertices in lattice-index units -> world: linear along the lattice edge, in float64 (exact for a uniform axis up
+        to its fp32 values)."""
         cols = []
         for a in range(3):
             ax = axes[a].double()
             lo = v[:, a].floor().long().clamp_(0, max(len(ax) - 2, 0))
             hi = (lo + 1).clamp_(max=len(ax) - 1)
             cols.append(ax[lo] + (ax[hi] - ax[lo]) * (v[:, a] - lo.double()))
-        vw = torch.stack(cols, dim=1) if len(v) else v
+        return torch.stack(cols, dim=1) if len(v) else v
+
+    def _simplified(self, v, t, c, axes, cell):
+        """extract_mesh's arrays of the simplified mesh.  Device backend: simplified on the device, one copy of the small mesh;
+        host backend: the numpy path on the full mesh's host arrays."""
+        from .mesh_simplify import simplify_mesh
+        if self.backend == "device":
+            out = simplify_mesh(self._world(v, axes), t, cell, colors=c, backend="device", device=v.device, return_tensors=True)
+            out = [to_host(x).numpy() for x in out]
+        else:
+            full = self._mesh_to_host(v, t, c, axes)
+            out = simplify_mesh(full[0], full[1], cell, colors=full[2] if c is not None else None, backend="host")
+        return (out[0].astype(np.float64), out[1].astype(np.int64)) + tuple(out[2:])
+
+    @staticmethod
+    def _mesh_to_host(v, t, c, axes):
+        """Device mesh in lattice-index units (+ uint8 vertex colours or None) -> extract_mesh's numpy arrays, one copy."""
+        parts = []
+        if c is not None:
+            c = c.reshape(-1)
+            parts = [torch.cat([c, c.new_zeros((-c.numel()) % 8)]).view(torch.int64)]
+        vw = FusionVolume._world(v, axes)
         both = to_host(torch.cat([vw.reshape(-1).view(torch.int64), t.reshape(-1).to(torch.int64)] + parts))
         nv, nt = vw.numel(), t.numel()
         out = (both[:nv].view(torch.float64).numpy().reshape(-1, 3), both[nv:nv + nt].numpy().reshape(-1, 3))
@@ -1017,9 +1038,9 @@ class SparseFusionVolume(FusionVolume):
         bricks, table, tsdf, weight, color = self.finalize()._state
         return tsdf, weight, color, table, self.n_bricks > 0
 
-    def extract_mesh(self, isovalue=0.0):
+    def extract_mesh(self, isovalue=0.0, simplify_cell=None):
         """FusionVolume.extract_mesh's arrays, the same mesh in the same order, for -1 < isovalue < 1 (ValueError otherwise: the
-        allocation covers only what such an isovalue can cut).  Runs on the GPU whatever the backend."""
+        allocation covers only what such an isovalue can cut).  Runs on the GPU whatever the backend.  simplify_cell: as there."""
         if not -1.0 < float(isovalue) < 1.0:
             raise ValueError("FusionVolume(sparse=True).extract_mesh: -1 < isovalue < 1")
         self.finalize()
@@ -1038,4 +1059,4 @@ class SparseFusionVolume(FusionVolume):
         band = ops.Band(self.res, table, None, bricks, ops.fuse_band_values(tsdf, weight), {}, shape=self.shape)
         v, t = ops.marching_cubes_band(band, float(isovalue), observed_only=True)
         c = None if color is None else ops.fuse_vertex_colors_bricks(v, color, table, self.shape)
-        return self._mesh_to_host(v, t, c, axes)
+        return self._mesh_to_host(v, t, c, axes) if simplify_cell is None else self._simplified(v, t, c, axes, simplify_cell)

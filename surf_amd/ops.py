@@ -1719,6 +1719,106 @@ def clean_update_faces(vertices, faces, keep, compact_vertices=True):
 
 
 # ------------------------------------------------------------------------------------------------
+# mesh simplification (mesh_simplify.hip): vertex clustering with quadric placement; the rule is in include/surf_hip.h
+# ------------------------------------------------------------------------------------------------
+
+SIMPLIFY_HOST_READS = 2          # simplify_mesh waits for the device twice: see its docstring
+
+
+def simplify_mesh(vertices, faces, cell, normals=None, colors=None, stages=None):
+    """The surf_simplify_* rule on device tensors: vertices (n, 3) fp32, faces (m, 3) int32, optional normals (n, 3) fp32 and
+    colors (n, 3) uint8 -> (vertices (k, 3) fp32, faces (j, 3) int32, normals or None, colors or None, vertex_map (n,) int32).
+    The sorts, scans and searches between the kernels are torch's.  Exactly SIMPLIFY_HOST_READS reads of the device, each one
+    small copy: (1) [number of cells, limit flag, smallest and largest face index], (2) [kept faces, used cells]; an empty mesh
+    reads nothing.  A vertex outside the rule's lattice, or a face index outside the vertex list, raises ValueError after (1).
+    stages: a list that receives (name, start event, end event) per stage (scripts/time_simplify.py)."""
+    _chk(vertices, torch.float32, "vertices")
+    _chk(faces, torch.int32, "faces")
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"simplify_mesh: expected (n, 3) vertices and (m, 3) faces, got {tuple(vertices.shape)}, {tuple(faces.shape)}")
+    n, m, dev = vertices.shape[0], faces.shape[0], vertices.device
+    if max(n, m) > (2 ** 31 - 1) // 3:
+        _lib.check(-2, f"simplify_mesh: {n} vertices / {m} faces")
+    for t, dtype, name in ((normals, torch.float32, "normals"), (colors, torch.uint8, "colors")):
+        if t is not None:
+            _chk(t, dtype, name)
+            if tuple(t.shape) != (n, 3):
+                raise ValueError(f"simplify_mesh: {name} {tuple(t.shape)} for {n} vertices")
+    cell = float(cell)
+    if not (cell > 0 and 0 < cell * cell < float("inf")):
+        raise ValueError(f"simplify_mesh: cell must be finite and > 0, got {cell}")
+
+    def empty():
+        return (vertices.new_empty(0, 3), faces.new_empty(0, 3), None if normals is None else normals.new_empty(0, 3),
+                None if colors is None else colors.new_empty(0, 3), torch.full((n,), -1, dtype=torch.int32, device=dev))
+
+    if n == 0 or m == 0:
+        return empty()
+
+    def stage(name):
+        if stages is not None:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            if stages:
+                stages[-1] = stages[-1][:2] + (ev,)
+            if name is not None:
+                stages.append((name, ev, None))
+
+    L, s = _lib.lib(), _stream()
+    stage("keys+sort")
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    L.surf_simplify_keys(_p(vertices), n, cell, _p(keys), _p(flag), s)
+    skeys, vorder = torch.sort(keys, stable=True)                      # stable: a cell lists its vertices in index order
+    head = torch.ones(n, dtype=torch.bool, device=dev)
+    head[1:] = skeys[1:] != skeys[:-1]
+    rank = torch.cumsum(head, 0, dtype=torch.int64) - 1
+    f_lo, f_hi = torch.aminmax(faces)
+    n_cells, bad, lo, hi = torch.stack([rank[-1] + 1, flag[0].long(), f_lo.long(), f_hi.long()]).tolist()       # host read 1
+    if bad:
+        raise ValueError(f"simplify_mesh: a vertex is not finite or lies outside the 2^21 cells of {cell} per axis "
+                         "(surf_simplify_keys: exceeds a SURF_MAX_* limit)")
+    if lo < 0 or hi >= n:
+        raise ValueError(f"face indices span [{lo}, {hi}], the mesh has {n} vertices")
+    stage("faces")
+    vcell = torch.empty(n, dtype=torch.int32, device=dev)
+    vstart = torch.empty(n_cells + 1, dtype=torch.int64, device=dev)
+    L.surf_simplify_segments(_p(skeys), _p(vorder), _p(rank), n, n_cells, _p(vcell), _p(vstart), s)
+    fcell = torch.empty(m, 3, dtype=torch.int32, device=dev)
+    L.surf_simplify_face_cells(_p(faces), m, _p(vcell), n, _p(fcell), _p(flag), s)
+    slots = 1024
+    while slots < 2 * m:
+        slots <<= 1
+    owner = torch.empty(slots, dtype=torch.int32, device=dev)
+    face_slot = torch.empty(m, dtype=torch.int32, device=dev)
+    keep = torch.empty(m, dtype=torch.uint8, device=dev)
+    L.surf_simplify_faces(_p(fcell), m, _p(owner), slots, _p(face_slot), _p(keep), s)
+    used = torch.zeros(n_cells, dtype=torch.uint8, device=dev)
+    L.surf_simplify_mark_used(_p(fcell), _p(keep), m, n_cells, _p(used), s)
+    fscan = torch.cumsum(keep, 0, dtype=torch.int64)
+    cscan = torch.cumsum(used, 0, dtype=torch.int64)
+    n_f, n_v = torch.stack([fscan[-1], cscan[-1]]).tolist()                                                 # host read 2
+    if n_f == 0:
+        stage(None)
+        return empty()
+    stage("corner sort")
+    scell, corder = torch.sort(fcell.reshape(-1), stable=True)         # stable: a cell lists its corners in (face, corner) order
+    cstart = torch.searchsorted(scell, torch.arange(n_cells + 1, dtype=torch.int32, device=dev))     # int64; no host read
+    stage("cells")
+    out_v = torch.empty(n_v, 3, dtype=torch.float32, device=dev)
+    out_n = None if normals is None else torch.empty(n_v, 3, dtype=torch.float32, device=dev)
+    out_c = None if colors is None else torch.empty(n_v, 3, dtype=torch.uint8, device=dev)
+    L.surf_simplify_cells(_p(vertices), _p(normals), _p(colors), n, _p(faces), m, cell, _p(skeys), _p(vorder), _p(vstart),
+                          _p(corder), _p(cstart), n_cells, _p(used), _p(cscan), _p(out_v), _p(out_n), _p(out_c), s)
+    stage("compact")
+    out_f = torch.empty(n_f, 3, dtype=torch.int32, device=dev)
+    vmap = torch.empty(n, dtype=torch.int32, device=dev)
+    L.surf_simplify_compact(_p(fcell), _p(keep), _p(fscan), m, _p(vcell), n, _p(used), _p(cscan), n_cells, _p(out_f), _p(vmap), s)
+    stage(None)
+    return out_v, out_f, out_n, out_c, vmap
+
+
+# ------------------------------------------------------------------------------------------------
 # the DTU protocol's mesh cleaner (dtu_clean.hip): elliptical dilation, rounded projection into padded masks, vertex removal
 # ------------------------------------------------------------------------------------------------
 
