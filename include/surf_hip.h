@@ -1140,6 +1140,75 @@ int surf_simplify_compact(const int32_t* face_cells, const uint8_t* keep, const 
                           const int32_t* vertex_cell, int64_t n, const uint8_t* used, const int64_t* cell_scan, int64_t n_cells,
                           int32_t* out_faces, int32_t* vertex_map, void* stream);
 
+/*
+ * Point-cloud clean-up: the k nearest neighbours of every point of a cloud WITHIN the cloud, the outlier statistic and normals
+ * taken from them (surf_amd/point_filter.py, backend="device"; point_knn.hip).  Added under SURF_ABI_VERSION 41 without a bump,
+ * like the entry points above.  The device path returns the host path's arrays: both follow the rule below.  fp32 with separate
+ * multiplies and adds (-ffp-contract=off) in the stated order unless fp64 is named.  Open3D's remove_statistical_outlier /
+ * remove_radius_outlier / estimate_normals and PCL's StatisticalOutlierRemoval do the same jobs; the rule is RESTATED here, not
+ * pinned against either library.
+ *
+ * THE RULE.  P (n,3) fp32, n <= 2^31 - 1; 1 <= k <= SURF_POINTS_KNN_MAX_K; max_dist finite and > 0.
+ *   1. neighbours.  md2 = max_dist * max_dist (fp32, formed once on the host).  For a query i and a candidate j != i:
+ *      dx = P[j].x - P[i].x (dy, dz alike), d2 = (dx*dx + dy*dy) + dz*dz; j is admitted iff d2 <= md2.  A duplicate of P[i] at another
+ *      index is an ordinary neighbour at d2 = 0: only the index i itself is excluded.  A point with a non-finite coordinate is
+ *      nobody's neighbour and has no neighbours.  The list of i is the first k admitted candidates in ascending (d2, j) order (equal
+ *      d2: the smaller index first); count[i] is its length, 0 .. k.  The cell size of the search structure is not part of the rule.
+ *   2. statistic.  dist_m = sqrtf(d2_m); sum = ((dist_0 + dist_1) + ...) in list order; stat[i] = sum / (float)k if count[i] == k,
+ *      +inf otherwise (a STARVED point).
+ *   3. statistical rule.  Over the finite stat values, in fp64: N = their number, S = their sum, Q = the sum of their squares;
+ *      mu = S / N, sd = sqrt(max(Q / N - mu * mu, 0)), thr = mu + std_ratio * sd, keep[i] = (double)stat[i] <= thr.  Starved points
+ *      are dropped; with N == 0 nothing is kept.  surf_points_stat_sums forms N, S, Q by fixed-slot partial sums (below): the same
+ *      bits on every run, no float atomics.  The ORDER of that sum is the device's own: the host path adds the same numbers with
+ *      np.sum, so its thr may differ in the last bits (a mask differs only where a stat lies within ~1e-15 relative of thr).
+ *   4. radius rule.  keep[i] = count[i] == k, with k = the least number of neighbours and max_dist = the radius.
+ *   5. normals.  For a point with count >= 2: e_m = P[j_m] - P[i] (fp32, per component), then in fp64, sequentially in list order
+ *      from +0: S1[a] += e[a], S2[ab] += e[a] * e[b] for ab = 00 01 02 11 12 22.  The point itself contributes e = 0: m = count + 1,
+ *      M[a] = S1[a] / m, C[ab] = S2[ab] / m - M[a] * M[b].  The normal is the unit eigenvector of C's smallest eigenvalue by
+ *      SURF_POINTS_NORMAL_SWEEPS cyclic Jacobi sweeps over (p,q) = (0,1), (0,2), (1,2), V = I at the start, r the third index:
+ *        if C[pq] != 0:  theta = (C[qq] - C[pp]) / (2 * C[pq]);  t = 1 / (|theta| + sqrt(theta*theta + 1)), negated if theta < 0;
+ *                        c = 1 / sqrt(t*t + 1);  s = t * c;  h = t * C[pq];  C[pp] -= h;  C[qq] += h;  C[pq] = 0;
+ *                        (C[rp], C[rq]) = (c*C[rp] - s*C[rq], s*C[rp] + c*C[rq]);  the same for (V[ip], V[iq]), i = 0, 1, 2.
+ *      Column g of V with the smallest C[gg] (ties: the lowest g), divided by sqrt((x*x + y*y) + z*z), is n.
+ *      Orientation, with the fp64 centre c of the point's view (view[i] in [0, n_views)): d = (n.x*(c.x - P.x) + n.y*(c.y - P.y)) +
+ *      n.z*(c.z - P.z); n is negated if d < 0.  If d == 0, or without centres, n is negated iff its component of largest magnitude
+ *      (ties: the lowest axis) is negative.  n is rounded to fp32 once.  count < 2, or a result that is not finite: (0,0,0).
+ *
+ * Entry points, in the order surf_amd.ops calls them (the sort of the keys, bincount and cumsum between them are the caller's):
+ *   surf_points_knn_keys: keys (n) int64 = ((cx * ny) + cy) * nz + cz with c[a] = floor(((double)P[a] - lo[a]) / cell) clamped to the
+ *     grid, or nx*ny*nz for a point with a non-finite coordinate (it sorts behind the table and is never visited).
+ *     nx*ny*nz <= SURF_POINTS_KNN_MAX_CELLS (SURF_E_LIMIT beyond).
+ *   surf_points_knn: the lists.  sorted_points (n,3) = P in ascending key order, sorted_index (n) int32 = the caller's index of every
+ *     row of it, cell_start (nx*ny*nz + 1) int32 = the first row of every cell (cell_start[nx*ny*nz] = the number of finite points).
+ *     index (n,k) int32 padded with -1, d2 (n,k) fp32 padded with +inf, count (n) int32; every row is written.  One thread per
+ *     query in cell order; shells of cells around the query's own are walked until no unvisited point can enter the list (an equal
+ *     d2 with a smaller index included: the test is strict) or the shell's reach exceeds max_dist.  The k-slot list lives in LDS
+ *     (8 B per slot: d2's bits above the index, so that one integer comparison is the (d2, j) order).
+ *   surf_points_knn_reduce: the same search without writing the lists: stat (n) fp32, count (n) int32 and, if normal is given,
+ *     normal (n,3) fp32 by rule 5; points (n,3) = P in the caller's order (read for e_m).  view (n) int32 and centres (n_views,3)
+ *     fp64 on the DEVICE are given together or not at all (SURF_E_ARG otherwise); a view index outside [0, n_views) is oriented
+ *     as if there were no centres.
+ *   surf_points_stat_sums: out (3) fp64 = [N, S, Q] of rule 3.  partials: device scratch of SURF_POINTS_STAT_SLOTS * 3 fp64.
+ *     Workgroup w of min(ceil(n / 256), SURF_POINTS_STAT_SLOTS) adds its points (thread by thread in index order, then a fixed tree)
+ *     into slot w; one workgroup adds the slots in slot order.
+ * k outside [1, SURF_POINTS_KNN_MAX_K], a max_dist that is not finite and > 0 (or whose square is 0 or not finite), !(cell > 0) are
+ * SURF_E_ARG; n >= 2^31 is SURF_E_LIMIT; n == 0 returns 0 at once.
+ */
+#define SURF_POINTS_KNN_MAX_K 32
+#define SURF_POINTS_KNN_MAX_CELLS (1 << 26)
+#define SURF_POINTS_NORMAL_SWEEPS 8
+#define SURF_POINTS_STAT_SLOTS 1024
+int surf_points_knn_keys(const float* points, int64_t n, double lo_x, double lo_y, double lo_z, double cell, int64_t nx, int64_t ny,
+                         int64_t nz, int64_t* keys, void* stream);
+int surf_points_knn(const float* sorted_points, const int32_t* sorted_index, const int32_t* cell_start, int64_t n, double lo_x,
+                    double lo_y, double lo_z, double cell, int64_t nx, int64_t ny, int64_t nz, int k, float max_dist, int32_t* index,
+                    float* d2, int32_t* count, void* stream);
+int surf_points_knn_reduce(const float* points, const float* sorted_points, const int32_t* sorted_index, const int32_t* cell_start,
+                           int64_t n, double lo_x, double lo_y, double lo_z, double cell, int64_t nx, int64_t ny, int64_t nz, int k,
+                           float max_dist, const int32_t* view, const double* centres, int n_views, float* stat, int32_t* count,
+                           float* normal, void* stream);
+int surf_points_stat_sums(const float* stat, int64_t n, double* partials, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

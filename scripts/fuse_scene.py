@@ -16,6 +16,10 @@ protocol's cleaner (evaluation/clean_dtu.py) and evaluation.dtu_eval.evaluate_sc
 With --point_cloud the same depth maps are ALSO merged into one point cloud, one point per surface sample (fusion.fuse_points,
 csrc/point_cloud.hip, with the --min_consistent / --consistency_* flags) -> <out>/meshes/fused/scan<N>_points.ply, scored with
 the evaluator's point-cloud mode when --eval_dir is given; the mesh and its fields of the record are what they are without it.
+With --cloud_outliers K STD_RATIO (or --cloud_radius_outliers MIN_NEIGHBOURS) and --cloud_normals K the cloud is then cleaned
+(surf_amd/point_filter.py, csrc/point_knn.hip: k nearest neighbours within --cloud_max_dist): statistical (or radius) outlier
+removal first, then normals on what is left, turned towards the camera that saw each point; the filtered cloud is what goes to
+<N>_points.ply (with nx ny nz) and to the scores, and the record gains `cloud_filter` and `cloud_normals`.
 
 The lattice covers the union of the groups' normalised [-1, 1]^3 boxes (fusion.bounds_from_scale_mats; a first pass over the items
 reads their scale_mats) at --voxel_mm world units per step, or --resolution points along the longest side.
@@ -77,6 +81,18 @@ def parse_args(argv=None):
     ap.add_argument("--point_cloud", action="store_true",
                     help="also merge the depth maps into one point cloud (fusion.fuse_points: a pixel that --min_consistent other "
                          "views agree with is emitted once) and write meshes/fused/scan<N>_points.ply")
+    ap.add_argument("--cloud_outliers", nargs=2, default=None, metavar=("K", "STD_RATIO"),
+                    help="with --point_cloud: drop the points whose mean distance to their K nearest neighbours exceeds the cloud's "
+                         "mean + STD_RATIO standard deviations, and the points with fewer than K neighbours within --cloud_max_dist "
+                         "(surf_amd/point_filter.py, csrc/point_knn.hip)")
+    ap.add_argument("--cloud_radius_outliers", type=int, default=None, metavar="MIN_NEIGHBOURS",
+                    help="with --point_cloud: drop the points with fewer than MIN_NEIGHBOURS neighbours within --cloud_max_dist")
+    ap.add_argument("--cloud_normals", type=int, default=None, metavar="K",
+                    help="with --point_cloud: normals from the K nearest neighbours, turned towards the camera that saw the point; the "
+                         "PLY gains nx ny nz.  Runs after the outlier step, on what is left")
+    ap.add_argument("--cloud_max_dist", type=float, default=None,
+                    help="search radius of the three cloud steps in world units (default: 10 lattice steps; a guess - the record's "
+                         "`starved` count says when it is too small)")
     ap.add_argument("--clean_mesh", action="store_true",
                     help="the DTU evaluation protocol's cleaner on the world-frame mesh (evaluation/clean_dtu.py; needs --dtu_test_dir)")
     ap.add_argument("--dtu_test_dir", default=None, help="DTU_TEST tree (cameras/, scan<N>/mask/) of --clean_mesh")
@@ -129,6 +145,15 @@ def run(args, state=None):
         raise SystemExit("fuse_scene: --tnt_dir needs --scene")
     if args.clean_mesh and args.dtu_test_dir is None:
         raise SystemExit("fuse_scene: --clean_mesh needs --dtu_test_dir")
+    # a caller may build the Namespace by hand without the cloud steps' attributes
+    cloud_outliers, cloud_radius = getattr(args, "cloud_outliers", None), getattr(args, "cloud_radius_outliers", None)
+    cloud_normals, cloud_max_dist = getattr(args, "cloud_normals", None), getattr(args, "cloud_max_dist", None)
+    cloud_steps = cloud_outliers is not None or cloud_radius is not None or cloud_normals is not None
+    cloud_records = {}
+    if cloud_steps and not args.point_cloud:
+        raise SystemExit("fuse_scene: --cloud_outliers, --cloud_radius_outliers and --cloud_normals need --point_cloud")
+    if cloud_outliers is not None and cloud_radius is not None:
+        raise SystemExit("fuse_scene: one of --cloud_outliers and --cloud_radius_outliers")
     cfg = C.parse_file(args.conf)
     dconf = cfg["val_dataset"]
     if args.data_dir is not None:
@@ -208,7 +233,16 @@ def run(args, state=None):
                                    device=dev)
         ms["points"] = 1e3 * (time.perf_counter() - t0)
         points_path = os.path.join(args.out_dir, "meshes", "fused", f"{name}_points.ply")
-        mesh_io.write_ply_points(points_path, cloud.points, cloud.colors)
+        if cloud_steps:
+            # ---- outliers first, normals on what is left: the filtered cloud is what is written and scored ----
+            from surf_amd import point_filter
+            max_dist = cloud_max_dist if cloud_max_dist is not None else 10.0 * voxel
+            ratio = None if cloud_outliers is None else (int(cloud_outliers[0]), float(cloud_outliers[1]))
+            cloud, cloud_nrm, cloud_records = point_filter.clean_step(cloud, cloud_views, outliers=ratio, radius_outliers=cloud_radius,
+                                                                      normals_k=cloud_normals, max_dist=max_dist, device=dev)
+            mesh_io.write_ply_points(points_path, cloud.points, cloud.colors, normals=cloud_nrm)
+        else:
+            mesh_io.write_ply_points(points_path, cloud.points, cloud.colors)
         cloud_views.clear()
     filtered = None
     if args.min_consistent > 0:
@@ -298,6 +332,7 @@ def run(args, state=None):
         rec.update(min_consistent=args.min_consistent, kept_share=sum(filtered["kept"]) / max(sum(filtered["measured"]), 1))
     if cloud is not None:
         rec.update(points=int(len(cloud.points)), points_file=points_path)
+        rec.update(cloud_records)                       # cloud_filter / cloud_normals: without the flags the record is what it was
     if args.eval_dir is not None:
         t0 = time.perf_counter()
         d2s, s2d, overall = dtu_eval.evaluate_scan(mesh_path, args.eval_dir, args.scan, patch_size=args.patch_size,

@@ -77,10 +77,11 @@ def write_ply(path, vertices, triangles, normals=None, colors=None):
         f.write(faces.tobytes())
 
 
-def write_ply_points(path, points, colors=None):
-    """A point cloud (fusion.fuse_points) as write_ply's file with `element face 0`: points (N,3), colors (N,3) uint8 or None.
-    datasets.mvs_io.read_ply_points and read_ply read it back."""
-    write_ply(path, points, np.zeros((0, 3), dtype=np.int32), colors=colors)
+def write_ply_points(path, points, colors=None, normals=None):
+    """A point cloud (fusion.fuse_points) as write_ply's file with `element face 0`: points (N,3), colors (N,3) uint8 or None,
+    normals (N,3) float32 or None (point_filter.estimate_normals: nx ny nz, what a viewer shades by and a Poisson reconstructor
+    needs).  datasets.mvs_io.read_ply_points and read_ply read it back."""
+    write_ply(path, points, np.zeros((0, 3), dtype=np.int32), normals=normals, colors=colors)
 
 
 _PLY_TYPES = {"float": "<f4", "float32": "<f4", "double": "<f8", "float64": "<f8", "uchar": "u1", "uint8": "u1", "char": "i1",

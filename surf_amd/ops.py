@@ -3090,3 +3090,142 @@ def weight_norm_backward(vs, gs, dWs):
     _lib.lib().surf_weight_norm_backward(n, _ptr_array(vs), _ptr_array(gs), _ptr_array(dWs), rows, cols, _ptr_array(dvs),
                                          _ptr_array(dgs), _stream())
     return dvs, dgs
+
+
+# ------------------------------------------------------------------------------------------------
+# point-cloud clean-up (point_knn.hip): k nearest neighbours within a cloud, outlier statistic, normals
+# ------------------------------------------------------------------------------------------------
+
+POINTS_KNN_MAX_K = 32                # SURF_POINTS_KNN_MAX_K of include/surf_hip.h
+POINTS_KNN_MAX_CELLS = 1 << 26       # SURF_POINTS_KNN_MAX_CELLS
+POINTS_STAT_SLOTS = 1024             # SURF_POINTS_STAT_SLOTS
+
+
+def _chk_knn(k, max_dist, what):
+    """The argument checks of the surf_points_knn* entry points, as ValueError before the call."""
+    if int(k) != k or not 1 <= k <= POINTS_KNN_MAX_K:
+        raise ValueError(f"{what}: k must be an integer in [1, {POINTS_KNN_MAX_K}], got {k}")
+    md = float(np.float32(max_dist))
+    md2 = float(np.float32(md) * np.float32(md))
+    if not (md > 0 and np.isfinite(md) and md2 > 0 and np.isfinite(md2)):
+        raise ValueError(f"{what}: max_dist must be finite and > 0 (and so must its fp32 square), got {max_dist}")
+    return int(k), md
+
+
+class PointKnnTable:
+    """The dense cell table over one cloud (n, 3) fp32 that surf_points_knn / _reduce search: nearest_dist_capped's pattern (a key
+    kernel, torch's sort, bincount and cumsum), the cell grown by 1.25 until the table has at most POINTS_KNN_MAX_CELLS cells.
+    Points with a non-finite coordinate sort behind the table.  cell: the cell size to start from (tests; the results do not depend
+    on it), default: about four cells per point by the box's volume, at least max_dist / 16 (an isolated point walks at most 17
+    shells).  Two host syncs (the box of the finite points)."""
+
+    def __init__(self, points, max_dist, cell=None):
+        _chk(points, torch.float32, "points")
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError(f"points: expected (n, 3), got {tuple(points.shape)}")
+        n = points.shape[0]
+        if n > 2 ** 31 - 1:
+            raise ValueError(f"points: {n} points exceed int32 indexing")
+        if n == 0:
+            raise ValueError("PointKnnTable: empty cloud")
+        dev = points.device
+        finite = points[torch.isfinite(points).all(1)]
+        if finite.shape[0]:
+            lo, hi = finite.amin(0).double().tolist(), finite.amax(0).double().tolist()
+        else:
+            lo, hi = [0.0, 0.0, 0.0], [0.0, 0.0, 0.0]
+        del finite
+        ext = [b - a for a, b in zip(lo, hi)]
+        if cell is None:
+            pad = max(ext) * 1e-3 or 1.0              # flat or single-point clouds still get a box of some volume
+            vol = (ext[0] + pad) * (ext[1] + pad) * (ext[2] + pad)
+            cell = max((vol / (4.0 * n)) ** (1.0 / 3.0), float(max_dist) / 16.0)
+        cell = float(cell)
+        if not (cell > 0 and np.isfinite(cell)):
+            raise ValueError(f"PointKnnTable: cell must be finite and > 0, got {cell}")
+        while True:
+            dims = [int(e // cell) + 1 for e in ext]
+            if dims[0] * dims[1] * dims[2] <= POINTS_KNN_MAX_CELLS:
+                break
+            cell *= 1.25
+        ncell = dims[0] * dims[1] * dims[2]
+        keys = torch.empty(n, dtype=torch.int64, device=dev)
+        _lib.lib().surf_points_knn_keys(_p(points), n, lo[0], lo[1], lo[2], cell, dims[0], dims[1], dims[2], _p(keys), _stream())
+        skeys, order = torch.sort(keys)
+        self.cstart = torch.zeros(ncell + 1, dtype=torch.int32, device=dev)
+        self.cstart[1:] = torch.cumsum(torch.bincount(skeys, minlength=ncell + 1)[:ncell], 0)
+        self.points = points
+        self.spts = points[order].contiguous()
+        self.sidx = order.to(torch.int32)
+        self.lo, self.cell, self.dims, self.n = lo, cell, dims, n
+        self.cells_per_point = ncell / n
+
+    def _grid(self):
+        return (self.lo[0], self.lo[1], self.lo[2], self.cell, self.dims[0], self.dims[1], self.dims[2])
+
+
+def _knn_table(points, max_dist, cell):
+    return points if isinstance(points, PointKnnTable) else PointKnnTable(points, max_dist, cell)
+
+
+def points_knn(points, k, max_dist, cell=None):
+    """The neighbour lists of rule 1 (include/surf_hip.h): (index (n, k) int32 padded with -1, d2 (n, k) fp32 padded with +inf, count
+    (n,) int32) of a cloud (n, 3) fp32 on the device, or of a PointKnnTable over it."""
+    k, max_dist = _chk_knn(k, max_dist, "points_knn")
+    if not isinstance(points, PointKnnTable) and points.shape[0] == 0:
+        _chk(points, torch.float32, "points")
+        dev = points.device
+        return (torch.empty(0, k, dtype=torch.int32, device=dev), torch.empty(0, k, dtype=torch.float32, device=dev),
+                torch.empty(0, dtype=torch.int32, device=dev))
+    T = _knn_table(points, max_dist, cell)
+    dev = T.spts.device
+    index = torch.empty(T.n, k, dtype=torch.int32, device=dev)
+    d2 = torch.empty(T.n, k, dtype=torch.float32, device=dev)
+    count = torch.empty(T.n, dtype=torch.int32, device=dev)
+    _lib.lib().surf_points_knn(_p(T.spts), _p(T.sidx), _p(T.cstart), T.n, *T._grid(), k, max_dist, _p(index), _p(d2), _p(count),
+                               _stream())
+    return index, d2, count
+
+
+def points_knn_reduce(points, k, max_dist, normals=False, view=None, centres=None, cell=None):
+    """The same search without the lists: (stat (n,) fp32, count (n,) int32, normal (n, 3) fp32 or None) by rules 2 and 5.
+    view (n,) int32 and centres (n_views, 3) fp64 (device tensors, both or neither) orient the normals."""
+    k, max_dist = _chk_knn(k, max_dist, "points_knn_reduce")
+    if (view is None) != (centres is None):
+        raise ValueError("points_knn_reduce: view and centres are given together")
+    if view is not None and not normals:
+        raise ValueError("points_knn_reduce: view / centres orient normals: pass normals=True")
+    if not isinstance(points, PointKnnTable) and points.shape[0] == 0:
+        _chk(points, torch.float32, "points")
+        dev = points.device
+        return (torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.int32, device=dev),
+                torch.empty(0, 3, dtype=torch.float32, device=dev) if normals else None)
+    T = _knn_table(points, max_dist, cell)
+    dev = T.spts.device
+    n_views = 0
+    if view is not None:
+        _chk(view, torch.int32, "view")
+        _chk(centres, torch.float64, "centres")
+        if view.shape != (T.n,):
+            raise ValueError(f"view: expected ({T.n},), got {tuple(view.shape)}")
+        if centres.dim() != 2 or centres.shape[1] != 3 or centres.shape[0] < 1:
+            raise ValueError(f"centres: expected (n_views >= 1, 3), got {tuple(centres.shape)}")
+        n_views = centres.shape[0]
+    stat = torch.empty(T.n, dtype=torch.float32, device=dev)
+    count = torch.empty(T.n, dtype=torch.int32, device=dev)
+    normal = torch.empty(T.n, 3, dtype=torch.float32, device=dev) if normals else None
+    _lib.lib().surf_points_knn_reduce(_p(T.points), _p(T.spts), _p(T.sidx), _p(T.cstart), T.n, *T._grid(), k, max_dist, _p(view),
+                                      _p(centres), n_views, _p(stat), _p(count), _p(normal), _stream())
+    return stat, count, normal
+
+
+def points_stat_sums(stat):
+    """(3,) float64 device tensor [number, sum, sum of squares] of the finite values of stat (n,) fp32 (rule 3): fixed-slot partial
+    sums added in slot order, the same bits on every run."""
+    _chk(stat, torch.float32, "stat")
+    if stat.dim() != 1:
+        raise ValueError(f"stat: expected (n,), got {tuple(stat.shape)}")
+    part = torch.empty(POINTS_STAT_SLOTS * 3, dtype=torch.float64, device=stat.device)
+    out = torch.empty(3, dtype=torch.float64, device=stat.device)
+    _lib.lib().surf_points_stat_sums(_p(stat), stat.shape[0], _p(part), _p(out), _stream())
+    return out
