@@ -480,6 +480,8 @@ extern "C" int surf_matching_depth_backward(const float* mvol, int D, int nv, co
     return SURF_E_ARG;
   if (D < 2 || H < 1 || W < 1 || h < 1 || w < 1 || n < 1) return SURF_E_ARG;
   if (nv < 1 || nv > SURF_MAX_VIEWS) return SURF_E_LIMIT;
+  if (view0 < 0 || view0 >= nv || view1 >= nv) return SURF_E_ARG;
+  if ((int64_t)D * D * D > 0x7fffffffLL) return SURF_E_LIMIT;    // 31-bit cell keys in the workgroup's LDS table (D <= 1290)
   MatchArgs a;
   a.mvol = mvol; a.D = D; a.nv = nv; a.H = H; a.W = W; a.h = h; a.w = w; a.lin_x = lin_x; a.lin_y = lin_y; a.lin_n = lin_n;
   a.n = n; a.pre = pre_depths; a.ratio_cur = ratio_cur; a.ratio_prev = ratio_prev; a.jitter = jitter; a.out = nullptr;
@@ -491,8 +493,6 @@ extern "C" int surf_matching_depth_backward(const float* mvol, int D, int nv, co
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(upsample_bilinear_bwd_kernel, dim3((unsigned)((n_full + 255) / 256)), dim3(256), 0, st, g_full, nv, h, w, H,
                      W, g_lr);
-  if (view0 < 0 || view0 >= nv || view1 >= nv) return SURF_E_ARG;
-  if ((int64_t)D * D * D > 0x7fffffffLL) return SURF_E_LIMIT;    // 31-bit cell keys in the workgroup's LDS table (D <= 1290)
   const int64_t tiles = (int64_t)((w + MB_TX - 1) / MB_TX) * ((h + MB_TY - 1) / MB_TY);
   const bool two = view1 >= 0 && view1 != view0;
   hipLaunchKernelGGL(matching_depth_bwd_kernel, dim3((unsigned)(tiles * (two ? 2 : 1))), dim3(256), 0, st, a, g_lr, dmvol, view0,

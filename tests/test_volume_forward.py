@@ -91,15 +91,16 @@ def depth_filtering_ref(depths, coords, D, intrs, c2ws, dt=F64):
     return torch.stack(rows, dim=1)                              # (4, nv, N)
 
 
-def back_proj_ref(agg, feats_c2f, coords, D, intrs, c2ws, stage, dt=F64):
-    """-> [mean | var] rows (N,8), the mask inputs (3, nv, N) = nx, ny, qz, and the agg_mlp pre-activations (nv, N, 8)."""
+def back_proj_ref(agg, feats_c2f, coords, D, intrs, c2ws, stage, dt=F64, ndc=None):
+    """-> [mean | var] rows (N,8), the mask inputs (3, nv, N) = nx, ny, qz, and the agg_mlp pre-activations (nv, N, 8).
+    ndc: a projection to use in place of _ndc (same signature)."""
     nv = feats_c2f[-1].shape[0]
     h, w = feats_c2f[-1].shape[-2:]
     w1, b1, w2, b2 = (t.to(dt) for t in agg)
     world = _world(coords, D, dt)
     warp, logits, terms, pres = [], [], [], []
     for v in range(nv):
-        nx, ny, qz = _ndc(world, intrs[v], c2ws[v], h, w, dt)
+        nx, ny, qz = (ndc or _ndc)(world, intrs[v], c2ws[v], h, w, dt)
         m = (nx.abs() <= 1) & (ny.abs() <= 1) & (qz > 0)
         f = torch.zeros(coords.shape[0], 4, dtype=dt)
         for lvl in feats_c2f[stage:]:
@@ -134,9 +135,10 @@ def _trilinear(vol, g):
     return out
 
 
-def matching_ref(mvol, intrs, c2ws, near_fars, H, W, res_level, n, pre=None, ratio_cur=1.0, ratio_prev=1.0, dt=F64):
+def matching_ref(mvol, intrs, c2ws, near_fars, H, W, res_level, n, pre=None, ratio_cur=1.0, ratio_prev=1.0, dt=F64, jitter=None):
     """The matching field's expected depth: low-resolution maps (nv,h,w), full-resolution maps (nv,H,W) and, with `pre`, the four
-    arguments the band construction compares with zero, (nv, h*w, 4) = b - far and a - near of the two bands."""
+    arguments the band construction compares with zero, (nv, h*w, 4) = b - far and a - near of the two bands.
+    jitter (nv, h*w, 2): the train-mode shift per ray and band, z += jitter * (band's range) / n."""
     h, w = H // res_level, W // res_level
     py, px = torch.meshgrid(torch.linspace(0, H - 1, h), torch.linspace(0, W - 1, w), indexing="ij")   # fp32 positions: inputs
     px, py = px.reshape(-1), py.reshape(-1)
@@ -154,10 +156,12 @@ def matching_ref(mvol, intrs, c2ws, near_fars, H, W, res_level, n, pre=None, rat
         cz = (rd @ torch.inverse(R).t())[:, 2]
         if pre is None:
             z = n0 + (f0 - n0) * lin[None, :].expand(px.shape[0], -1)
+            if jitter is not None:
+                z = z + jitter[v, :, 0:1].to(dt) * (f0 - n0) / n
         else:
             zc = (pre[v].to(dt)[py.long(), px.long()] / cz)[:, None]
             zs, arg = [], []
-            for r in (ratio_cur, ratio_prev):
+            for k, r in enumerate((ratio_cur, ratio_prev)):
                 half = ((f0 - n0) * r) / 2
                 a, b = zc - half, zc + half
                 arg.append(b - f0)
@@ -165,7 +169,7 @@ def matching_ref(mvol, intrs, c2ws, near_fars, H, W, res_level, n, pre=None, rat
                 arg.append(a - n0)
                 b = torch.where(a < n0, b + (n0 - a), b)
                 a, b = torch.clamp(a, n0, f0), torch.clamp(b, n0, f0)
-                zs.append(a + (b - a) * lin[None, :])
+                zs.append(a + (b - a) * lin[None, :] + (0.0 if jitter is None else jitter[v, :, k:k + 1].to(dt) * (b - a) / n))
             z = torch.cat(zs, dim=-1)
             args.append(torch.cat(arg, dim=-1))
         pts = (ro[None, None, :] + rd[:, None, :] * z[..., None]).reshape(-1, 3)
@@ -242,10 +246,11 @@ def _intr(f, H, W):
 INSIDE_POS = (0.15, -0.1, -0.83)                                 # inside the unit cube: the voxels with z < -0.83 lie behind it
 
 
-def make_cameras(nv, H, W, exact_first=False):
+def make_cameras(nv, H, W, exact_first=False, per_axis_focal=False):
     """Ring cameras around the origin with a focal length that leaves the cube's corners outside the image, one camera INSIDE the
     unit cube (second ring slot), and - exact_first - an axis-aligned first view whose matrices are dyadic: the voxels (+-1, y, 0)
-    of an odd lattice project to |nx| = 1 exactly.  -> intrs, c2ws (nv,4,4) fp32, near_fars (nv,2) fp32."""
+    of an odd lattice project to |nx| = 1 exactly.  per_axis_focal: the vertical focal length scaled by (H - 1) / (W - 1), for images
+    far from square (the same share of the cube in view along both axes).  -> intrs, c2ws (nv,4,4) fp32, near_fars (nv,2) fp32."""
     c2ws, intrs = [], []
     if exact_first:
         c = np.eye(4)
@@ -262,6 +267,9 @@ def make_cameras(nv, H, W, exact_first=False):
             c2ws.append(_look_at((2.2 * np.cos(ang), 0.5 * np.sin(1.7 * k + 0.4), 2.2 * np.sin(ang)), (0.03 * k, -0.02 * k, 0.0)))
             intrs.append(_intr(0.77 * (W - 1), H, W))
         k += 1
+    if per_axis_focal:
+        for K in intrs:
+            K[1, 1] *= (H - 1) / (W - 1)
     c2ws = torch.from_numpy(np.stack(c2ws)).to(F32)
     dist = c2ws[:, :3, 3].norm(dim=1)
     near_fars = torch.stack([(dist - 1.0).clamp(min=0.2), dist + 1.0], dim=1)
@@ -348,10 +356,11 @@ COSTVOL_CASES = ((2, None, 0, 1),
                  (34, 1000, 1, 2))
 
 
-def make_agg(seed):
+def make_agg(seed, dt=F32):
+    """dt = float64: drawn in float64 and rounded to fp32 once (the same bits on every host)."""
     g = torch.Generator().manual_seed(seed)
-    return (torch.randn(8, 4, generator=g) * 0.7, torch.randn(8, generator=g) * 0.5, torch.randn(1, 8, generator=g) * 0.7,
-            torch.randn(1, generator=g) * 0.3)
+    return tuple(t.to(F32) for t in (torch.randn(8, 4, generator=g, dtype=dt) * 0.7, torch.randn(8, generator=g, dtype=dt) * 0.5,
+                                     torch.randn(1, 8, generator=g, dtype=dt) * 0.7, torch.randn(1, generator=g, dtype=dt) * 0.3))
 
 
 def agg_state_dict(agg):
@@ -359,15 +368,16 @@ def agg_state_dict(agg):
             "volume.agg_mlp.2.bias": agg[3]}
 
 
-def make_pyramid(nv, seed):
-    """Four levels (nv,4,h,w) coarse -> fine whose contents differ per level: a smooth field of its own plus its own offset."""
+def make_pyramid(nv, seed, levels=LEVELS_C2F, dt=F32):
+    """Four levels (nv,4,h,w) coarse -> fine whose contents differ per level: a smooth field of its own plus its own offset.
+    dt = float64: computed in float64 and rounded to fp32 once (the same bits on every host)."""
     g = torch.Generator().manual_seed(seed)
     out = []
-    for l, (h, w) in enumerate(LEVELS_C2F):
-        ys, xs = torch.meshgrid(torch.linspace(0, 1, h), torch.linspace(0, 1, w), indexing="ij")
-        ph = torch.rand(nv, 4, 1, 1, generator=g) * 6.28
+    for l, (h, w) in enumerate(levels):
+        ys, xs = torch.meshgrid(torch.linspace(0, 1, h, dtype=dt), torch.linspace(0, 1, w, dtype=dt), indexing="ij")
+        ph = torch.rand(nv, 4, 1, 1, generator=g, dtype=dt) * 6.28
         smooth = torch.sin((3.0 + l) * xs[None, None] + ph) * torch.cos((2.0 + 1.5 * l) * ys[None, None] - ph)
-        out.append((0.6 * smooth + 0.15 * torch.randn(nv, 4, h, w, generator=g) + 0.25 * (l - 1.5)).contiguous())
+        out.append((0.6 * smooth + 0.15 * torch.randn(nv, 4, h, w, generator=g, dtype=dt) + 0.25 * (l - 1.5)).to(F32).contiguous())
     return out
 
 
