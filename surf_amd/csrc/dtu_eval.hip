@@ -18,11 +18,11 @@
 #include <math.h>
 
 #include "common.h"
+#include "nearest_shell.h"     // the shell walk and kGridAxis, shared with fscore.hip
 
 namespace {
 
 constexpr int kUndecided = 0, kKept = 1, kRemoved = 2;
-constexpr int64_t kThinAxis = int64_t(1) << 21;   // cells per axis of the thinning grid: keys (x << 42) | (y << 21) | z
 
 struct Tri {
   double o[3], v1[3], v2[3];
@@ -137,12 +137,12 @@ __global__ __launch_bounds__(256) void thin_round_kernel(ThinArgs a) {
   if (load_state(&a.state[i]) != kUndecided) return;
   const double px = a.spts[t * 3 + 0], py = a.spts[t * 3 + 1], pz = a.spts[t * 3 + 2];
   const int64_t key = a.ucell[a.scell[t]];
-  const int64_t cx = key >> 42, cy = (key >> 21) & (kThinAxis - 1), cz = key & (kThinAxis - 1);
+  const int64_t cx = key >> 42, cy = (key >> 21) & (kGridAxis - 1), cz = key & (kGridAxis - 1);
   bool pending = false;
-  for (int64_t x = max(cx - 1, (int64_t)0); x <= min(cx + 1, kThinAxis - 1); ++x)
-    for (int64_t y = max(cy - 1, (int64_t)0); y <= min(cy + 1, kThinAxis - 1); ++y) {
+  for (int64_t x = max(cx - 1, (int64_t)0); x <= min(cx + 1, kGridAxis - 1); ++x)
+    for (int64_t y = max(cy - 1, (int64_t)0); y <= min(cy + 1, kGridAxis - 1); ++y) {
       const int64_t col = (x << 42) | (y << 21);
-      const int64_t kend = col | min(cz + 1, kThinAxis - 1);
+      const int64_t kend = col | min(cz + 1, kGridAxis - 1);
       for (int64_t c = lower_bound(a.ucell, a.ncell, col | max(cz - 1, (int64_t)0)); c < a.ncell && a.ucell[c] <= kend; ++c) {
         const int32_t e = a.cstart[c + 1];
         for (int32_t s = a.cstart[c]; s < e; ++s) {
@@ -161,64 +161,6 @@ __global__ __launch_bounds__(256) void thin_round_kernel(ThinArgs a) {
     }
   if (pending) atomicAdd(a.undecided, 1);
   else store_state(&a.state[i], kKept);
-}
-
-struct NearestArgs {
-  const double* q;         // (m, 3) queries
-  int64_t m;
-  const double* ref;       // (r, 3) reference points in cell order
-  const int32_t* cstart;   // (nx*ny*nz + 1) first point of every cell
-  double lo[3], cell, max_dist;
-  int64_t nc[3];
-  double* out;             // (m) distance, +inf where >= max_dist
-};
-
-__global__ __launch_bounds__(256) void nearest_kernel(NearestArgs a) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= a.m) return;
-  const double p[3] = {a.q[t * 3 + 0], a.q[t * 3 + 1], a.q[t * 3 + 2]};
-  // shells beyond kmax lie farther than max_dist (with a margin for the rounding of the cell coordinates)
-  const int64_t kmax = (int64_t)ceil(a.max_dist / (a.cell * (1.0 - 1e-6))) + 1;
-  int64_t c[3];
-  int64_t gap = 0;                           // Chebyshev distance in cells from the query's cell to the grid
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double f = floor((p[k] - a.lo[k]) / a.cell);
-    const double g = f < 0.0 ? -f : f - (double)(a.nc[k] - 1);
-    if (!(g <= (double)kmax)) {              // far outside (or NaN): nothing within max_dist
-      a.out[t] = INFINITY;
-      return;
-    }
-    c[k] = (int64_t)f;
-    gap = max(gap, (int64_t)max(g, 0.0));
-  }
-  const int64_t zlo = 0, zhi = a.nc[2] - 1;
-  double best = INFINITY;
-  for (int64_t k = gap; k <= kmax; ++k) {
-    // shells 0 .. k-1 are visited (those below `gap` miss the grid): every other point lies more than k-1 cells away.  Stop
-    // once the best is within that reach, or the reach is max_dist.
-    const double reach = (double)(k > 0 ? k - 1 : 0) * a.cell * (1.0 - 1e-6);
-    if (best <= reach * reach || reach >= a.max_dist) break;
-    const int64_t x0 = max(c[0] - k, (int64_t)0), x1 = min(c[0] + k, a.nc[0] - 1);
-    const int64_t y0 = max(c[1] - k, (int64_t)0), y1 = min(c[1] + k, a.nc[1] - 1);
-    for (int64_t x = x0; x <= x1; ++x)
-      for (int64_t y = y0; y <= y1; ++y) {
-        // on the rim of the shell's x-y square the whole z column belongs to the shell, inside it only the two z faces
-        const bool rim = x == c[0] - k || x == c[0] + k || y == c[1] - k || y == c[1] + k;
-        const int64_t z0 = rim ? max(c[2] - k, zlo) : c[2] - k, z1 = rim ? min(c[2] + k, zhi) : c[2] + k;
-        for (int64_t z = z0; z <= z1; z += rim ? 1 : 2 * k) {
-          if (z < zlo || z > zhi) continue;
-          const int64_t cell = (x * a.nc[1] + y) * a.nc[2] + z;
-          const int32_t e = a.cstart[cell + 1];
-          for (int32_t s = a.cstart[cell]; s < e; ++s) {
-            const double dx = p[0] - a.ref[(int64_t)s * 3 + 0], dy = p[1] - a.ref[(int64_t)s * 3 + 1], dz = p[2] - a.ref[(int64_t)s * 3 + 2];
-            best = fmin(best, (dx * dx + dy * dy) + dz * dz);
-          }
-        }
-      }
-  }
-  const double d = sqrt(best);
-  a.out[t] = d < a.max_dist ? d : INFINITY;
 }
 
 inline unsigned blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
@@ -244,7 +186,7 @@ extern "C" int surf_dtu_sample_write(const double* vertices, const int64_t* tria
 extern "C" int surf_dtu_cell_keys(const double* points, int64_t n, double lo_x, double lo_y, double lo_z, double cell, int64_t nx,
                                   int64_t ny, int64_t nz, int64_t* keys, void* stream) {
   if (!points || !keys || n <= 0 || !(cell > 0.0) || nx <= 0 || ny <= 0 || nz <= 0) return SURF_E_ARG;
-  if (nx > kThinAxis || ny > kThinAxis || nz > kThinAxis) return SURF_E_LIMIT;
+  if (nx > kGridAxis || ny > kGridAxis || nz > kGridAxis) return SURF_E_LIMIT;
   hipLaunchKernelGGL(cell_keys_kernel, dim3(blocks(n)), dim3(256), 0, (hipStream_t)stream, points, n, lo_x, lo_y, lo_z, cell, nx, ny,
                      nz, keys);
   return surf_check_launch();
@@ -267,8 +209,8 @@ extern "C" int surf_dtu_nearest(const double* queries, int64_t m, const double* 
                                 double lo_y, double lo_z, double cell, int64_t nx, int64_t ny, int64_t nz, double max_dist, double* out,
                                 void* stream) {
   if (!queries || !sorted_ref || !cell_start || !out || m <= 0 || !(cell > 0.0) || !(max_dist > 0.0)) return SURF_E_ARG;
-  if (nx <= 0 || ny <= 0 || nz <= 0 || nx > kThinAxis || ny > kThinAxis || nz > kThinAxis) return SURF_E_ARG;
+  if (nx <= 0 || ny <= 0 || nz <= 0 || nx > kGridAxis || ny > kGridAxis || nz > kGridAxis) return SURF_E_ARG;
   NearestArgs a{queries, m, sorted_ref, cell_start, {lo_x, lo_y, lo_z}, cell, max_dist, {nx, ny, nz}, out};
-  hipLaunchKernelGGL(nearest_kernel, dim3(blocks(m)), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL((surf_nearest_kernel<false, NearestArgs>), dim3(blocks(m)), dim3(256), 0, (hipStream_t)stream, a);
   return surf_check_launch();
 }

@@ -8,19 +8,19 @@
 //    the two other axes: ((v_i > v) != (v_j > v)) and u < (u_j - u_i) * (v - v_i) / (v_j - v_i) + u_i.
 //  * voxel mean: the members of a voxel are summed sequentially in input-index order (the caller's stable sort by cell key keeps
 //    that order inside a segment), one thread per (voxel, coordinate); then sum / count.  A segment may be of any length.
-//  * nearest: nearest_kernel of dtu_eval.hip (the same shells over the same dense cell table, the same (dx*dx + dy*dy) + dz*dz and
-//    one sqrt) that also tracks the reference point's index in the caller's order; equal squared distances go to the smaller index.
-//  * ICP sums: per-workgroup partial sums into fixed slots (the grid depends on n alone, every thread adds its points in index
-//    order, the workgroup's tree is fixed), then one workgroup adds the slots in slot order: the same bits on every run, no float
-//    atomics.  Pass 1: pair count, sum of source, sum of target, sum of d*d; pass 2: the CENTRED 3x3 cross-covariance.
+//  * nearest: the shell walk of nearest_shell.h, which dtu_eval.hip runs too (the same shells over the same dense cell table, the
+//    same (dx*dx + dy*dy) + dz*dz and one sqrt), here tracking the reference point's index in the caller's order as well; equal
+//    squared distances go to the smaller index.
+//  * ICP sums: the fixed-slot partial sums of slot_sums.h (the same bits on every run, no float atomics).  Pass 1: pair count, sum of source, sum of target, sum of d*d; pass 2: the CENTRED 3x3 cross-covariance.
 // Offline evaluation: gather- and fp64-VALU bound, one item per thread, 256 threads.
 #include <math.h>
 
 #include "common.h"
+#include "nearest_shell.h"     // the shell walk and kGridAxis, shared with dtu_eval.hip
+#include "slot_sums.h"         // block_partial, slot_finish_kernel, slots_for, shared with point_knn.hip
 
 namespace {
 
-constexpr int64_t kAxis = int64_t(1) << 21;      // cells per axis: keys (x << 42) | (y << 21) | z, as the thinning grid's
 constexpr int kSlots = SURF_FSCORE_ICP_SLOTS;    // workgroups (= partial-sum slots) of an ICP reduction, at most
 
 struct Rigid {
@@ -54,9 +54,9 @@ __global__ __launch_bounds__(256) void voxel_keys_kernel(const double* __restric
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   // the entry point has checked the box: the clamp only keeps a NaN or a point outside the stated box inside the key's fields
-  const int64_t cx = min(max((int64_t)floor((P[i * 3 + 0] - ox) / voxel), (int64_t)0), kAxis - 1);
-  const int64_t cy = min(max((int64_t)floor((P[i * 3 + 1] - oy) / voxel), (int64_t)0), kAxis - 1);
-  const int64_t cz = min(max((int64_t)floor((P[i * 3 + 2] - oz) / voxel), (int64_t)0), kAxis - 1);
+  const int64_t cx = min(max((int64_t)floor((P[i * 3 + 0] - ox) / voxel), (int64_t)0), kGridAxis - 1);
+  const int64_t cy = min(max((int64_t)floor((P[i * 3 + 1] - oy) / voxel), (int64_t)0), kGridAxis - 1);
+  const int64_t cz = min(max((int64_t)floor((P[i * 3 + 2] - oz) / voxel), (int64_t)0), kGridAxis - 1);
   keys[i] = (cx << 42) | (cy << 21) | cz;
 }
 
@@ -76,94 +76,7 @@ __global__ __launch_bounds__(256) void voxel_mean_kernel(const double* __restric
   out[t] = acc / (double)(e - b);
 }
 
-struct NearestArgs {
-  const double* q;         // (m, 3) queries
-  int64_t m;
-  const double* ref;       // (r, 3) reference points in cell order
-  const int32_t* ridx;     // (r) their index in the caller's order
-  const int32_t* cstart;   // (nx*ny*nz + 1) first point of every cell
-  double lo[3], cell, max_dist;
-  int64_t nc[3];
-  double* out;             // (m) distance, +inf where >= max_dist
-  int64_t* index;          // (m) index of the nearest reference point, -1 there
-};
-
-// dtu_eval.hip's nearest_kernel with the index carried along
-__global__ __launch_bounds__(256) void nearest_index_kernel(NearestArgs a) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= a.m) return;
-  const double p[3] = {a.q[t * 3 + 0], a.q[t * 3 + 1], a.q[t * 3 + 2]};
-  // shells beyond kmax lie farther than max_dist (with a margin for the rounding of the cell coordinates)
-  const int64_t kmax = (int64_t)ceil(a.max_dist / (a.cell * (1.0 - 1e-6))) + 1;
-  int64_t c[3];
-  int64_t gap = 0;                           // Chebyshev distance in cells from the query's cell to the grid
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double f = floor((p[k] - a.lo[k]) / a.cell);
-    const double g = f < 0.0 ? -f : f - (double)(a.nc[k] - 1);
-    if (!(g <= (double)kmax)) {              // far outside (or NaN): nothing within max_dist
-      a.out[t] = INFINITY;
-      a.index[t] = -1;
-      return;
-    }
-    c[k] = (int64_t)f;
-    gap = max(gap, (int64_t)max(g, 0.0));
-  }
-  const int64_t zlo = 0, zhi = a.nc[2] - 1;
-  double best = INFINITY;
-  int32_t besti = INT32_MAX;
-  for (int64_t k = gap; k <= kmax; ++k) {
-    // shells 0 .. k-1 are visited: every other point lies more than k-1 cells away.  Stop once the best is STRICTLY within that
-    // reach (a point at exactly the reach could still tie with a smaller index), or the reach is max_dist.
-    const double reach = (double)(k > 0 ? k - 1 : 0) * a.cell * (1.0 - 1e-6);
-    if (best < reach * reach || reach >= a.max_dist) break;
-    const int64_t x0 = max(c[0] - k, (int64_t)0), x1 = min(c[0] + k, a.nc[0] - 1);
-    const int64_t y0 = max(c[1] - k, (int64_t)0), y1 = min(c[1] + k, a.nc[1] - 1);
-    for (int64_t x = x0; x <= x1; ++x)
-      for (int64_t y = y0; y <= y1; ++y) {
-        // on the rim of the shell's x-y square the whole z column belongs to the shell, inside it only the two z faces
-        const bool rim = x == c[0] - k || x == c[0] + k || y == c[1] - k || y == c[1] + k;
-        const int64_t z0 = rim ? max(c[2] - k, zlo) : c[2] - k, z1 = rim ? min(c[2] + k, zhi) : c[2] + k;
-        for (int64_t z = z0; z <= z1; z += rim ? 1 : 2 * k) {
-          if (z < zlo || z > zhi) continue;
-          const int64_t cell = (x * a.nc[1] + y) * a.nc[2] + z;
-          const int32_t e = a.cstart[cell + 1];
-          for (int32_t s = a.cstart[cell]; s < e; ++s) {
-            const double dx = p[0] - a.ref[(int64_t)s * 3 + 0], dy = p[1] - a.ref[(int64_t)s * 3 + 1], dz = p[2] - a.ref[(int64_t)s * 3 + 2];
-            const double d2 = (dx * dx + dy * dy) + dz * dz;
-            const int32_t j = a.ridx[s];
-            if (d2 < best || (d2 == best && j < besti)) {
-              best = d2;
-              besti = j;
-            }
-          }
-        }
-      }
-  }
-  const double d = sqrt(best);
-  const bool near = d < a.max_dist;
-  a.out[t] = near ? d : INFINITY;
-  a.index[t] = near ? (int64_t)besti : -1;
-}
-
 // ---- the ICP reductions ----
-
-// K running sums of a thread -> the workgroup's sums in part[blockIdx.x * K ..]: xor butterflies inside the four wavefronts (a
-// fixed tree; every lane ends with the same bits), then the wavefronts' sums added in wavefront order.
-template <int K>
-__device__ __forceinline__ void block_partial(double (&acc)[K], double* __restrict__ part) {
-  __shared__ double wave[4][K];
-#pragma unroll
-  for (int k = 0; k < K; ++k)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int k = 0; k < K; ++k) wave[w][k] = acc[k];
-  __syncthreads();
-  if (threadIdx.x < K) part[(int64_t)blockIdx.x * K + threadIdx.x] = ((wave[0][threadIdx.x] + wave[1][threadIdx.x]) + wave[2][threadIdx.x]) + wave[3][threadIdx.x];
-}
 
 struct PairArgs {
   const double* src;       // (n, 3) transformed source points
@@ -213,17 +126,7 @@ __global__ __launch_bounds__(256) void icp_cov_kernel(PairArgs a) {
   block_partial<9>(acc, a.part);
 }
 
-// one workgroup: thread k adds slot 0, 1, ... of sum k
-__global__ __launch_bounds__(64) void icp_finish_kernel(const double* __restrict__ part, int slots, int K, double* __restrict__ out) {
-  const int k = threadIdx.x;
-  if (k >= K) return;
-  double acc = 0.0;
-  for (int s = 0; s < slots; ++s) acc += part[(int64_t)s * K + k];
-  out[k] = acc;
-}
-
 inline unsigned blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
-inline int slots_for(int64_t n) { return (int)((n + 255) / 256 < kSlots ? (n + 255) / 256 : kSlots); }
 
 }  // namespace
 
@@ -257,7 +160,7 @@ extern "C" int surf_fscore_voxel_keys(const double* points, int64_t n, const dou
   for (int k = 0; k < 3; ++k) {
     if (!(h_lo[k] <= h_hi[k])) return SURF_E_ARG;                     // NaN included
     origin[k] = h_lo[k] - voxel / 2;
-    if (!(floor((h_hi[k] - origin[k]) / voxel) < (double)kAxis)) return SURF_E_LIMIT;
+    if (!(floor((h_hi[k] - origin[k]) / voxel) < (double)kGridAxis)) return SURF_E_LIMIT;
   }
   hipLaunchKernelGGL(voxel_keys_kernel, dim3(blocks(n)), dim3(256), 0, (hipStream_t)stream, points, n, origin[0], origin[1], origin[2],
                      voxel, keys);
@@ -279,9 +182,9 @@ extern "C" int surf_fscore_nearest(const double* queries, int64_t m, const doubl
   if (!queries || !sorted_ref || !sorted_index || !cell_start || !out || !index || m <= 0 || !(cell > 0.0) || !(max_dist > 0.0))
     return SURF_E_ARG;
   if (nx <= 0 || ny <= 0 || nz <= 0) return SURF_E_ARG;
-  if (m > INT32_MAX || nx > kAxis || ny > kAxis || nz > kAxis) return SURF_E_LIMIT;
-  NearestArgs a{queries, m, sorted_ref, sorted_index, cell_start, {lo_x, lo_y, lo_z}, cell, max_dist, {nx, ny, nz}, out, index};
-  hipLaunchKernelGGL(nearest_index_kernel, dim3(blocks(m)), dim3(256), 0, (hipStream_t)stream, a);
+  if (m > INT32_MAX || nx > kGridAxis || ny > kGridAxis || nz > kGridAxis) return SURF_E_LIMIT;
+  NearestIndexArgs a{queries, m, sorted_ref, sorted_index, cell_start, {lo_x, lo_y, lo_z}, cell, max_dist, {nx, ny, nz}, out, index};
+  hipLaunchKernelGGL((surf_nearest_kernel<true, NearestIndexArgs>), dim3(blocks(m)), dim3(256), 0, (hipStream_t)stream, a);
   return surf_check_launch();
 }
 
@@ -290,9 +193,9 @@ extern "C" int surf_fscore_icp_sums(const double* source, const double* target, 
   if (!source || !target || !index || !dist || !partials || !out || n <= 0 || n_target <= 0) return SURF_E_ARG;
   if (n > INT32_MAX || n_target > INT32_MAX) return SURF_E_LIMIT;
   PairArgs a{source, target, index, dist, n, n_target, {0, 0, 0}, {0, 0, 0}, partials};
-  const int slots = slots_for(n);
+  const int slots = slots_for(n, kSlots);
   hipLaunchKernelGGL(icp_sums_kernel, dim3(slots), dim3(256), 0, (hipStream_t)stream, a);
-  hipLaunchKernelGGL(icp_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)partials, slots, 8, out);
+  hipLaunchKernelGGL(slot_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)partials, slots, 8, out);
   return surf_check_launch();
 }
 
@@ -302,8 +205,8 @@ extern "C" int surf_fscore_icp_cov(const double* source, const double* target, i
   if (n > INT32_MAX || n_target > INT32_MAX) return SURF_E_LIMIT;
   PairArgs a{source, target, index, nullptr, n, n_target, {h_centroids[0], h_centroids[1], h_centroids[2]},
              {h_centroids[3], h_centroids[4], h_centroids[5]}, partials};
-  const int slots = slots_for(n);
+  const int slots = slots_for(n, kSlots);
   hipLaunchKernelGGL(icp_cov_kernel, dim3(slots), dim3(256), 0, (hipStream_t)stream, a);
-  hipLaunchKernelGGL(icp_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)partials, slots, 9, out);
+  hipLaunchKernelGGL(slot_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)partials, slots, 9, out);
   return surf_check_launch();
 }

@@ -36,18 +36,9 @@
 #include <math.h>
 
 #include "common.h"
+#include "fuse_rule.h"       // the per-point rules (integration, vertex colour) and the view table, shared with fuse_sparse.hip
 
 namespace {
-
-struct FuseView {
-  float P[12];
-  const float* depth;
-  const float* image;
-  int H, W;
-  float dscale;
-  int pad;
-};
-struct FuseViews { FuseView v[SURF_FUSE_MAX_VIEWS]; };
 
 template <bool COLOR>
 __global__ __launch_bounds__(256) void fuse_integrate_kernel(float* __restrict__ tsdf, float* __restrict__ weight,
@@ -60,38 +51,7 @@ __global__ __launch_bounds__(256) void fuse_integrate_kernel(float* __restrict__
   if (r >= plane) return;
   const uint32_t j = r / (uint32_t)nz, k = r - j * (uint32_t)nz;
   const int64_t i = (int64_t)blockIdx.y * plane + r;
-  const float px = ax[blockIdx.y], py = ay[j], pz = az[k];
-  float ts = tsdf[i], w = weight[i];
-  float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
-  if (COLOR) { c0 = color[i * 3 + 0]; c1 = color[i * 3 + 1]; c2 = color[i * 3 + 2]; }
-  const float w0 = w;
-  for (int v = 0; v < n_views; ++v) {
-    const FuseView& V = views.v[v];
-    const float cx = ((V.P[0] * px + V.P[1] * py) + V.P[2] * pz) + V.P[3];
-    const float cy = ((V.P[4] * px + V.P[5] * py) + V.P[6] * pz) + V.P[7];
-    const float cz = ((V.P[8] * px + V.P[9] * py) + V.P[10] * pz) + V.P[11];
-    if (!(cz > 0.0f)) continue;
-    const float rx = rintf(cx / cz), ry = rintf(cy / cz);
-    if (!(rx >= 0.0f && rx <= (float)(V.W - 1) && ry >= 0.0f && ry <= (float)(V.H - 1))) continue;
-    const int64_t pix = (int64_t)(int)ry * V.W + (int)rx;
-    const float d = V.depth[pix] * V.dscale;
-    if (!(d > 0.0f && d <= FLT_MAX)) continue;
-    const float diff = d - cz;
-    if (!(diff >= -trunc)) continue;
-    const float t = fminf(diff / trunc, 1.0f);
-    const float wn = w + 1.0f;
-    ts = (ts * w + t) / wn;
-    if (COLOR) {
-      c0 = (c0 * w + V.image[pix * 3 + 0]) / wn;
-      c1 = (c1 * w + V.image[pix * 3 + 1]) / wn;
-      c2 = (c2 * w + V.image[pix * 3 + 2]) / wn;
-    }
-    w = wn;
-  }
-  if (w == w0) return;                            // no view observed the point: its state is unchanged, nothing to write
-  tsdf[i] = ts;
-  weight[i] = w;
-  if (COLOR) { color[i * 3 + 0] = c0; color[i * 3 + 1] = c1; color[i * 3 + 2] = c2; }
+  surf_fuse_integrate_point<COLOR>(tsdf, weight, color, i, ax[blockIdx.y], ay[j], az[k], views, n_views, trunc);
 }
 
 __global__ __launch_bounds__(256) void fuse_lattice_kernel(const float* __restrict__ tsdf, const float* __restrict__ weight, int64_t n,
@@ -101,33 +61,20 @@ __global__ __launch_bounds__(256) void fuse_lattice_kernel(const float* __restri
   u[i] = weight[i] > 0.0f ? -tsdf[i] : __builtin_nanf("");
 }
 
+// the dense colour lattice (nx, ny, nz, 3) as surf_fuse_vertex_color reads it
+struct DenseColors {
+  const float* __restrict__ color;
+  int ny, nz;
+  __device__ __forceinline__ int64_t locate(int x, int y, int z) const { return (((int64_t)x * ny + y) * nz + z) * 3; }
+  __device__ __forceinline__ float read(int64_t a, int c) const { return color[a + c]; }
+};
+
 __global__ __launch_bounds__(256) void fuse_vertex_colors_kernel(const double* __restrict__ vertices, int64_t n_vertices,
                                                                  const float* __restrict__ color, int nx, int ny, int nz,
                                                                  uint8_t* __restrict__ out) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n_vertices) return;
-  const int dims[3] = {nx, ny, nz};
-  int lo[3], axis = 0;
-  float f = 0.0f;
-  bool found = false;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const double v = vertices[t * 3 + a];
-    const double fl = fmin(fmax(floor(v), 0.0), (double)(dims[a] - 1));    // a NaN coordinate lands on 0: every read stays inside
-    lo[a] = (int)fl;
-    const double fr = v - fl;
-    if (!found && fr != 0.0) { found = true; axis = a; f = (float)fr; }
-  }
-  int hi[3] = {lo[0], lo[1], lo[2]};
-  hi[axis] = min(lo[axis] + 1, dims[axis] - 1);
-  const int64_t a_lo = (((int64_t)lo[0] * ny + lo[1]) * nz + lo[2]) * 3, a_hi = (((int64_t)hi[0] * ny + hi[1]) * nz + hi[2]) * 3;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float cl = color[a_lo + c], ch = color[a_hi + c];
-    float q = (cl + (ch - cl) * f) * 256.0f;
-    q = fminf(fmaxf(q, 0.0f), 255.0f);
-    out[t * 3 + c] = (uint8_t)q;
-  }
+  surf_fuse_vertex_color(vertices, t, nx, ny, nz, DenseColors{color, ny, nz}, out);
 }
 
 inline bool blocks256(int64_t n, unsigned* blocks) {
@@ -151,20 +98,7 @@ extern "C" int surf_fuse_integrate(float* tsdf, float* weight, float* color, con
   unsigned blocks;
   if (!blocks256((int64_t)ny * nz, &blocks)) return SURF_E_LIMIT;
   FuseViews views;
-  for (int v = 0; v < n_views; ++v) {
-    FuseView& V = views.v[v];
-    const int H = h_hw[2 * v], W = h_hw[2 * v + 1];
-    if (!h_depths[v] || H < 1 || W < 1 || (color && !h_images[v])) return SURF_E_ARG;
-    if ((int64_t)H * W >= ((int64_t)1 << 31) / 3) return SURF_E_LIMIT;
-    for (int e = 0; e < 12; ++e) V.P[e] = h_P[12 * v + e];
-    V.depth = h_depths[v];
-    V.image = color ? h_images[v] : nullptr;
-    V.H = H;
-    V.W = W;
-    V.dscale = h_dscale[v];
-    V.pad = 0;
-  }
-  for (int v = n_views; v < SURF_FUSE_MAX_VIEWS; ++v) views.v[v] = FuseView{};
+  if (int e = surf_fill_fuse_views(views, color != nullptr, h_P, h_depths, h_images, h_hw, h_dscale, n_views)) return e;
   if (color)
     hipLaunchKernelGGL(fuse_integrate_kernel<true>, dim3(blocks, (unsigned)nx), dim3(256), 0, (hipStream_t)stream, tsdf, weight, color,
                        ax, ay, az, ny, nz, views, n_views, trunc);

@@ -52,7 +52,9 @@
 #include <math.h>
 
 #define MC_TABLE_QUAL __constant__
+#include "band.h"             // brick addressing, the observed-corner classification (shared with mesh_band / mcubes / ray_cast)
 #include "common.h"
+#include "fuse_rule.h"        // the per-point rules and the view table, shared with fuse.hip
 #include "mc_tables.h"
 
 namespace {
@@ -60,23 +62,12 @@ namespace {
 constexpr int MARK_MARGIN = 2;
 
 struct Lattice {
+  typedef int64_t id_t;  // the type brick ids are computed in (band.h)
   int nx, ny, nz;
   int nbp;  // bricks per axis of the table: ceil(max(nx, ny, nz) / 8)
 };
 
 struct Lift { float L[12]; };
-
-struct FuseView {
-  float P[12];
-  const float* depth;
-  const float* image;
-  int H, W;
-  float dscale;
-  int pad;
-};
-struct FuseViews { FuseView v[SURF_FUSE_MAX_VIEWS]; };
-
-__device__ __forceinline__ bool finite_f(float v) { return fabsf(v) <= FLT_MAX; }   // false for NaN and +-inf
 
 // #{i : a[i] < v} (strict = true) or #{i : a[i] <= v} of a strictly increasing array
 __device__ __forceinline__ int count_below(const float* __restrict__ a, int n, float v, bool strict) {
@@ -110,7 +101,7 @@ __global__ __launch_bounds__(256) void fuse_mark_bricks_kernel(const float* __re
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       const float X = ((lift.L[3 * k] * qx + lift.L[3 * k + 1] * qy) + lift.L[3 * k + 2] * sz) + lift.L[9 + k];
-      fin[k] = fin[k] && finite_f(X);
+      fin[k] = fin[k] && surf_finite_f(X);
       lo[k] = fminf(lo[k], X);
       hi[k] = fmaxf(hi[k], X);
     }
@@ -133,45 +124,7 @@ __global__ __launch_bounds__(256) void fuse_mark_bricks_kernel(const float* __re
   }
   for (int bx = b0[0]; bx <= b1[0]; ++bx)
     for (int by = b0[1]; by <= b1[1]; ++by)
-      for (int bz = b0[2]; bz <= b1[2]; ++bz) mark[((int64_t)bx * g.nbp + by) * g.nbp + bz] = 1;
-}
-
-// fuse_integrate_kernel's per-point loop (fuse.hip), operation for operation
-template <bool COLOR>
-__device__ __forceinline__ void integrate_point(float* __restrict__ tsdf, float* __restrict__ weight, float* __restrict__ color,
-                                                int64_t i, float px, float py, float pz, const FuseViews& views, int n_views,
-                                                float trunc) {
-  float ts = tsdf[i], w = weight[i];
-  float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
-  if (COLOR) { c0 = color[i * 3 + 0]; c1 = color[i * 3 + 1]; c2 = color[i * 3 + 2]; }
-  const float w0 = w;
-  for (int v = 0; v < n_views; ++v) {
-    const FuseView& V = views.v[v];
-    const float cx = ((V.P[0] * px + V.P[1] * py) + V.P[2] * pz) + V.P[3];
-    const float cy = ((V.P[4] * px + V.P[5] * py) + V.P[6] * pz) + V.P[7];
-    const float cz = ((V.P[8] * px + V.P[9] * py) + V.P[10] * pz) + V.P[11];
-    if (!(cz > 0.0f)) continue;
-    const float rx = rintf(cx / cz), ry = rintf(cy / cz);
-    if (!(rx >= 0.0f && rx <= (float)(V.W - 1) && ry >= 0.0f && ry <= (float)(V.H - 1))) continue;
-    const int64_t pix = (int64_t)(int)ry * V.W + (int)rx;
-    const float d = V.depth[pix] * V.dscale;
-    if (!(d > 0.0f && d <= FLT_MAX)) continue;
-    const float diff = d - cz;
-    if (!(diff >= -trunc)) continue;
-    const float t = fminf(diff / trunc, 1.0f);
-    const float wn = w + 1.0f;
-    ts = (ts * w + t) / wn;
-    if (COLOR) {
-      c0 = (c0 * w + V.image[pix * 3 + 0]) / wn;
-      c1 = (c1 * w + V.image[pix * 3 + 1]) / wn;
-      c2 = (c2 * w + V.image[pix * 3 + 2]) / wn;
-    }
-    w = wn;
-  }
-  if (w == w0) return;                            // no view observed the point: its state is unchanged, nothing to write
-  tsdf[i] = ts;
-  weight[i] = w;
-  if (COLOR) { color[i * 3 + 0] = c0; color[i * 3 + 1] = c1; color[i * 3 + 2] = c2; }
+      for (int bz = b0[2]; bz <= b1[2]; ++bz) mark[band_brick_id(g.nbp, bx, by, bz)] = 1;
 }
 
 template <bool COLOR>
@@ -181,65 +134,38 @@ __global__ __launch_bounds__(256) void fuse_integrate_bricks_kernel(float* __res
                                                                     const float* __restrict__ az, Lattice g, FuseViews views,
                                                                     int n_views, float trunc) {
   const int id = bricks[blockIdx.x];
-  const int bz = id % g.nbp, by = (id / g.nbp) % g.nbp, bx = id / (g.nbp * g.nbp);
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     const int l = (int)threadIdx.x + 256 * h;
-    const int x = bx * 8 + (l >> 6), y = by * 8 + ((l >> 3) & 7), z = bz * 8 + (l & 7);
+    int x, y, z;
+    band_point_xyz(g.nbp, id, l, x, y, z);
     if (x >= g.nx || y >= g.ny || z >= g.nz) continue;                  // past an upper face: never updated
-    integrate_point<COLOR>(tsdf, weight, color, (int64_t)blockIdx.x * 512 + l, ax[x], ay[y], az[z], views, n_views, trunc);
+    surf_fuse_integrate_point<COLOR>(tsdf, weight, color, (int64_t)blockIdx.x * 512 + l, ax[x], ay[y], az[z], views, n_views, trunc);
   }
 }
 
 // ---- the observed-corner rule on a band ------------------------------------------------------------------------------
-// band position of lattice point (x, y, z) (inside the lattice), or -1 when its brick is not allocated
-__device__ __forceinline__ int64_t band_pos(const Lattice& g, const int32_t* __restrict__ table, int x, int y, int z) {
-  const int32_t s = table[((int64_t)(x >> 3) * g.nbp + (y >> 3)) * g.nbp + (z >> 3)];
-  return s < 0 ? (int64_t)-1 : (int64_t)s * 512 + (((x & 7) << 6) | ((y & 7) << 3) | (z & 7));
-}
-__device__ __forceinline__ float band_val(const Lattice& g, const int32_t* __restrict__ table, const float* __restrict__ vals, int x,
-                                          int y, int z) {
-  const int64_t p = band_pos(g, table, x, y, z);
-  return p < 0 ? __builtin_nanf("") : vals[p];
-}
-
 __global__ __launch_bounds__(256) void band_classify_observed_kernel(const float* __restrict__ vals, const int32_t* __restrict__ table,
                                                                      const int32_t* __restrict__ bricks, int64_t n_slots, Lattice g,
                                                                      double iso, uint8_t* __restrict__ flags) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n_slots * 512) return;
-  const int id = bricks[t >> 9], l = (int)(t & 511);
-  const int bz = id % g.nbp, by = (id / g.nbp) % g.nbp, bx = id / (g.nbp * g.nbp);
-  const int x = bx * 8 + (l >> 6), y = by * 8 + ((l >> 3) & 7), z = bz * 8 + (l & 7);
+  int x, y, z;
+  band_point_xyz(g.nbp, bricks[t >> 9], (int)(t & 511), x, y, z);
   unsigned f = 0;
-  if (x < g.nx && y < g.ny && z < g.nz) {
-    const bool hx = x + 1 < g.nx, hy = y + 1 < g.ny, hz = z + 1 < g.nz;
-    const float v0 = vals[t];
-    const float v1 = hx ? band_val(g, table, vals, x + 1, y, z) : v0, v3 = hy ? band_val(g, table, vals, x, y + 1, z) : v0;
-    const float v4 = hz ? band_val(g, table, vals, x, y, z + 1) : v0;
-    const bool ok0 = finite_f(v0), in0 = (double)v0 <= iso;
-    if (hx && ok0 && finite_f(v1) && ((double)v1 <= iso) != in0) f |= 1u;
-    if (hy && ok0 && finite_f(v3) && ((double)v3 <= iso) != in0) f |= 2u;
-    if (hz && ok0 && finite_f(v4) && ((double)v4 <= iso) != in0) f |= 4u;
-    if (hx && hy && hz && ok0) {
-      float c[8];
-      c[0] = v0; c[1] = v1; c[3] = v3; c[4] = v4;
-      c[2] = band_val(g, table, vals, x + 1, y + 1, z);
-      c[5] = band_val(g, table, vals, x + 1, y, z + 1);
-      c[6] = band_val(g, table, vals, x + 1, y + 1, z + 1);
-      c[7] = band_val(g, table, vals, x, y + 1, z + 1);
-      unsigned cs = 0;
-      bool all = true;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        all = all && finite_f(c[k]);
-        cs |= ((double)c[k] <= iso ? 1u : 0u) << k;
-      }
-      if (all) f |= (unsigned)MC_NTRI[cs] << 3;
-    }
-  }
+  const auto at = [=](int cx, int cy, int cz) { return band_val(g, table, vals, cx, cy, cz); };
+  if (x < g.nx && y < g.ny && z < g.nz) f = surf_classify_observed(x, y, z, g.nx, g.ny, g.nz, vals[t], iso, at, MC_NTRI);
   flags[t] = (uint8_t)f;
 }
+
+// brick-major colours (n_slots * 512, 3) as surf_fuse_vertex_color reads them: a lattice point of a missing brick reads 0
+struct BrickColors {
+  const float* __restrict__ color;
+  const int32_t* __restrict__ table;
+  Lattice g;
+  __device__ __forceinline__ int64_t locate(int x, int y, int z) const { return band_pos(g, table, x, y, z); }
+  __device__ __forceinline__ float read(int64_t p, int c) const { return p < 0 ? 0.0f : color[p * 3 + c]; }
+};
 
 __global__ __launch_bounds__(256) void fuse_vertex_colors_bricks_kernel(const double* __restrict__ vertices, int64_t n_vertices,
                                                                         const float* __restrict__ color,
@@ -247,28 +173,7 @@ __global__ __launch_bounds__(256) void fuse_vertex_colors_bricks_kernel(const do
                                                                         uint8_t* __restrict__ out) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n_vertices) return;
-  const int dims[3] = {g.nx, g.ny, g.nz};
-  int lo[3], axis = 0;
-  float f = 0.0f;
-  bool found = false;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const double v = vertices[t * 3 + a];
-    const double fl = fmin(fmax(floor(v), 0.0), (double)(dims[a] - 1));    // a NaN coordinate lands on 0: every read stays inside
-    lo[a] = (int)fl;
-    const double fr = v - fl;
-    if (!found && fr != 0.0) { found = true; axis = a; f = (float)fr; }
-  }
-  int hi[3] = {lo[0], lo[1], lo[2]};
-  hi[axis] = min(lo[axis] + 1, dims[axis] - 1);
-  const int64_t p_lo = band_pos(g, table, lo[0], lo[1], lo[2]), p_hi = band_pos(g, table, hi[0], hi[1], hi[2]);
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float cl = p_lo < 0 ? 0.0f : color[p_lo * 3 + c], ch = p_hi < 0 ? 0.0f : color[p_hi * 3 + c];
-    float q = (cl + (ch - cl) * f) * 256.0f;
-    q = fminf(fmaxf(q, 0.0f), 255.0f);
-    out[t * 3 + c] = (uint8_t)q;
-  }
+  surf_fuse_vertex_color(vertices, t, g.nx, g.ny, g.nz, BrickColors{color, table, g}, out);
 }
 
 // the lattice in its cube: 0 or a status
@@ -316,20 +221,7 @@ extern "C" int surf_fuse_integrate_bricks(float* tsdf, float* weight, float* col
   if (int e = lattice_of(nx, ny, nz, g)) return e;
   if (n_slots * 512 >= ((int64_t)1 << 31)) return SURF_E_LIMIT;                          // int32 band positions
   FuseViews views;
-  for (int v = 0; v < n_views; ++v) {
-    FuseView& V = views.v[v];
-    const int H = h_hw[2 * v], W = h_hw[2 * v + 1];
-    if (!h_depths[v] || H < 1 || W < 1 || (color && !h_images[v])) return SURF_E_ARG;
-    if ((int64_t)H * W >= ((int64_t)1 << 31) / 3) return SURF_E_LIMIT;
-    for (int e = 0; e < 12; ++e) V.P[e] = h_P[12 * v + e];
-    V.depth = h_depths[v];
-    V.image = color ? h_images[v] : nullptr;
-    V.H = H;
-    V.W = W;
-    V.dscale = h_dscale[v];
-    V.pad = 0;
-  }
-  for (int v = n_views; v < SURF_FUSE_MAX_VIEWS; ++v) views.v[v] = FuseView{};
+  if (int e = surf_fill_fuse_views(views, color != nullptr, h_P, h_depths, h_images, h_hw, h_dscale, n_views)) return e;
   if (n_slots == 0) return 0;
   if (color)
     hipLaunchKernelGGL(fuse_integrate_bricks_kernel<true>, dim3((unsigned)n_slots), dim3(256), 0, (hipStream_t)stream, tsdf, weight,

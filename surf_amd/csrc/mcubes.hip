@@ -17,6 +17,7 @@
 #include <math.h>
 
 #define MC_TABLE_QUAL __constant__
+#include "band.h"              // surf_classify_observed, shared with fuse_sparse.hip's band_classify_observed_kernel
 #include "common.h"
 #include "mc_tables.h"
 
@@ -245,39 +246,14 @@ extern "C" int surf_mc_emit(const float* u, int nx, int ny, int nz, double iso, 
 // triangles name has its bit set).
 namespace {
 
-__device__ __forceinline__ bool mc_finite(float v) { return fabsf(v) <= 3.402823466e+38f; }   // false for NaN and +-inf
-
 __global__ __launch_bounds__(256) void mc_classify_observed_kernel(const float* __restrict__ u, McDims d, double iso,
                                                                    uint8_t* __restrict__ flags) {
   const int64_t n = (int64_t)d.nx * d.ny * d.nz;
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int z = (int)(i % d.nz), y = (int)((i / d.nz) % d.ny), x = (int)(i / ((int64_t)d.nz * d.ny));
-  const bool hx = x + 1 < d.nx, hy = y + 1 < d.ny, hz = z + 1 < d.nz;
-  const float v0 = u[i];
-  const float v1 = hx ? u[lin(d, x + 1, y, z)] : v0, v3 = hy ? u[lin(d, x, y + 1, z)] : v0, v4 = hz ? u[lin(d, x, y, z + 1)] : v0;
-  const bool ok0 = mc_finite(v0), in0 = (double)v0 <= iso;
-  unsigned f = 0;
-  if (hx && ok0 && mc_finite(v1) && ((double)v1 <= iso) != in0) f |= 1u;
-  if (hy && ok0 && mc_finite(v3) && ((double)v3 <= iso) != in0) f |= 2u;
-  if (hz && ok0 && mc_finite(v4) && ((double)v4 <= iso) != in0) f |= 4u;
-  if (hx && hy && hz) {
-    float c[8];
-    c[0] = v0; c[1] = v1; c[3] = v3; c[4] = v4;
-    c[2] = u[lin(d, x + 1, y + 1, z)];
-    c[5] = u[lin(d, x + 1, y, z + 1)];
-    c[6] = u[lin(d, x + 1, y + 1, z + 1)];
-    c[7] = u[lin(d, x, y + 1, z + 1)];
-    unsigned cs = 0;
-    bool all = true;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      all = all && mc_finite(c[k]);
-      cs |= ((double)c[k] <= iso ? 1u : 0u) << k;
-    }
-    if (all) f |= (unsigned)MC_NTRI[cs] << 3;
-  }
-  flags[i] = (uint8_t)f;
+  const auto at = [=](int cx, int cy, int cz) { return u[lin(d, cx, cy, cz)]; };
+  flags[i] = (uint8_t)surf_classify_observed(x, y, z, d.nx, d.ny, d.nz, u[i], iso, at, MC_NTRI);
 }
 
 }  // namespace

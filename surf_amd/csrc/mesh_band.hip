@@ -29,6 +29,7 @@
 #include <math.h>
 
 #define MC_TABLE_QUAL __constant__
+#include "band.h"              // brick ids, local indices, band_pos / band_val (shared with fuse_sparse.hip and ray_cast.hip)
 #include "common.h"
 #include "mc_tables.h"
 
@@ -37,33 +38,11 @@ namespace {
 constexpr int BAND_BLOCK = 1024;  // active entries per workgroup in emit (= MC_BLOCK of mcubes.hip: surf_mc_count's layout)
 
 struct BandDims {
+  typedef int id_t;  // brick ids are computed in int (band.h): n <= SURF_BAND_MAX_RES keeps nbp^3 below 2^31
   int n;    // lattice points per axis
   int nbp;  // bricks per axis in the table
   int nbc;  // bricks per axis that hold cells
 };
-
-__device__ __forceinline__ int brick_id(const BandDims& d, int x, int y, int z) {
-  return ((x >> 3) * d.nbp + (y >> 3)) * d.nbp + (z >> 3);
-}
-__device__ __forceinline__ int local_of(int x, int y, int z) { return ((x & 7) << 6) | ((y & 7) << 3) | (z & 7); }
-
-// band position of lattice point (x, y, z), or -1 when its brick is not evaluated
-__device__ __forceinline__ int64_t band_pos(const BandDims& d, const int32_t* __restrict__ table, int x, int y, int z) {
-  const int32_t s = table[brick_id(d, x, y, z)];
-  return s < 0 ? (int64_t)-1 : (int64_t)s * 512 + local_of(x, y, z);
-}
-// (a missing brick reads NaN, which is never inside: it cannot happen by construction, and the tests compare with the dense mesh)
-__device__ __forceinline__ float band_val(const BandDims& d, const int32_t* __restrict__ table, const float* __restrict__ vals, int x,
-                                          int y, int z) {
-  const int64_t p = band_pos(d, table, x, y, z);
-  return p < 0 ? __builtin_nanf("") : vals[p];
-}
-
-__device__ __forceinline__ void brick_xyz(const BandDims& d, int id, int& bx, int& by, int& bz) {
-  bz = id % d.nbp;
-  by = (id / d.nbp) % d.nbp;
-  bx = id / (d.nbp * d.nbp);
-}
 
 __device__ __forceinline__ bool inside(float v, double iso) { return (double)v <= iso; }
 
@@ -94,7 +73,7 @@ __global__ __launch_bounds__(256) void band_screen_kernel(const float* __restric
   }
   const double ex = (double)cax[bx + 1] - cax[bx], ey = (double)cay[by + 1] - cay[by], ez = (double)caz[bz + 1] - caz[bz];
   const double half_diag = 0.5 * sqrt(ex * ex + ey * ey + ez * ez);
-  if ((any_in && any_out) || amin <= margin * half_diag) mark[((int64_t)bx * d.nbp + by) * d.nbp + bz] = 1;
+  if ((any_in && any_out) || amin <= margin * half_diag) mark[band_brick_id(d.nbp, bx, by, bz)] = 1;
 }
 
 // ---- growth bookkeeping ---------------------------------------------------------------------------------------------
@@ -109,12 +88,12 @@ __global__ __launch_bounds__(256) void band_promote_kernel(uint8_t* __restrict__
   }
   is_cell[i] = 1;  // stays marked: the list of new cell bricks is surf_compact(mark)
   int bx, by, bz;
-  brick_xyz(d, (int)i, bx, by, bz);
+  band_brick_xyz(d.nbp, (int)i, bx, by, bz);
 #pragma unroll
   for (int k = 0; k < 8; ++k) {  // itself and the forward halo whose points its upper-face cells read
     const int x = bx + kCx[k], y = by + kCy[k], z = bz + kCz[k];
     if (x >= d.nbp || y >= d.nbp || z >= d.nbp) continue;
-    const int64_t j = ((int64_t)x * d.nbp + y) * d.nbp + z;
+    const int64_t j = band_brick_id(d.nbp, x, y, z);
     if (table[j] < 0) need[j] = 1;
   }
 }
@@ -145,7 +124,7 @@ __global__ __launch_bounds__(256) void band_grow_kernel(const float* __restrict_
   const int lx = l >> 6, ly = (l >> 3) & 7, lz = l & 7;
   if (!(lx == 0 || lx == 7 || ly == 0 || ly == 7 || lz == 0 || lz == 7)) return;
   int bx, by, bz;
-  brick_xyz(d, id, bx, by, bz);
+  band_brick_xyz(d.nbp, id, bx, by, bz);
   const int x = bx * 8 + lx, y = by * 8 + ly, z = bz * 8 + lz;
   const int last = d.n - 2;  // largest cell origin
   if (x > last || y > last || z > last) return;
@@ -162,7 +141,7 @@ __global__ __launch_bounds__(256) void band_grow_kernel(const float* __restrict_
       const int sb = s & 1, sc = s >> 1;
       const int cx = qx - (a == 0 ? 0 : sb), cy = qy - (a == 1 ? 0 : (a == 0 ? sb : sc)), cz = qz - (a == 2 ? 0 : sc);
       if (cx < 0 || cy < 0 || cz < 0 || cx > last || cy > last || cz > last) continue;
-      const int b = brick_id(d, cx, cy, cz);
+      const int b = band_brick_of<int>(d.nbp, cx, cy, cz);
       if (!is_cell[b]) mark[b] = 1;
     }
   }
@@ -175,7 +154,7 @@ __global__ __launch_bounds__(256) void band_points_kernel(const float* __restric
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= m * 512) return;
   int bx, by, bz;
-  brick_xyz(d, bricks[t >> 9], bx, by, bz);
+  band_brick_xyz(d.nbp, bricks[t >> 9], bx, by, bz);
   const int l = (int)(t & 511);
   const int last = d.n - 1;  // clipped points repeat the last lattice point (their values are never read)
   const int x = min(bx * 8 + (l >> 6), last), y = min(by * 8 + ((l >> 3) & 7), last), z = min(bz * 8 + (l & 7), last);
@@ -192,7 +171,7 @@ __device__ __forceinline__ bool edge_meshed(const BandDims& d, const uint8_t* __
     const int sb = s & 1, sc = s >> 1;
     const int cx = qx - (a == 0 ? 0 : sb), cy = qy - (a == 1 ? 0 : (a == 0 ? sb : sc)), cz = qz - (a == 2 ? 0 : sc);
     if (cx < 0 || cy < 0 || cz < 0 || cx > last || cy > last || cz > last) continue;
-    if (is_cell[brick_id(d, cx, cy, cz)]) return true;
+    if (is_cell[band_brick_of<int>(d.nbp, cx, cy, cz)]) return true;
   }
   return false;
 }
@@ -202,10 +181,9 @@ __global__ __launch_bounds__(256) void band_classify_kernel(const float* __restr
                                                             int64_t n_slots, BandDims d, double iso, uint8_t* __restrict__ flags) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n_slots * 512) return;
-  const int id = bricks[t >> 9], l = (int)(t & 511);
-  int bx, by, bz;
-  brick_xyz(d, id, bx, by, bz);
-  const int x = bx * 8 + (l >> 6), y = by * 8 + ((l >> 3) & 7), z = bz * 8 + (l & 7);
+  const int id = bricks[t >> 9];
+  int x, y, z;
+  band_point_xyz(d.nbp, id, (int)(t & 511), x, y, z);
   unsigned f = 0;
   if (x < d.n && y < d.n && z < d.n) {
     const bool cell = is_cell[id] != 0;
@@ -234,7 +212,7 @@ __global__ __launch_bounds__(256) void band_keys_kernel(const int32_t* __restric
   if (j >= m) return;
   const int32_t p = pos[j];
   int bx, by, bz;
-  brick_xyz(d, bricks[p >> 9], bx, by, bz);
+  band_brick_xyz(d.nbp, bricks[p >> 9], bx, by, bz);
   const int l = p & 511;
   const int64_t x = bx * 8 + (l >> 6), y = by * 8 + ((l >> 3) & 7), z = bz * 8 + (l & 7);
   keys[j] = (x * d.n + y) * d.n + z;

@@ -8,7 +8,7 @@
 //  * normals: fp64 S1 / S2 sums of the fp32 offsets in list order, covariance with the point itself counted, a fixed number of
 //    cyclic Jacobi sweeps (+ - * / sqrt only), the column of the smallest diagonal entry, oriented to the centre of the point's
 //    view; one rounding to fp32.
-//  * statistic sums: fixed-slot partial sums as fscore.hip's ICP reductions, no float atomics.
+//  * statistic sums: the fixed-slot partial sums of slot_sums.h, which fscore.hip's ICP reductions use too; no float atomics.
 //
 // The search structure is dtu_eval.hip's / fscore.hip's: a dense cell table (the caller sorts the keys and scans the counts), the
 // points permuted into cell order, ridx = their index in the caller's order so that the tie rule speaks the caller's indices.
@@ -29,6 +29,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "slot_sums.h"         // block_partial, slot_finish_kernel, slots_for, shared with fscore.hip
 
 namespace {
 
@@ -264,10 +265,9 @@ __global__ __launch_bounds__(kLanes) void knn_reduce_kernel(SearchArgs a, Reduce
   o.normal[(int64_t)i * 3 + 2] = nz;
 }
 
-// ---- rule 3's sums: [number, sum, sum of squares] of the finite statistics, fscore.hip's fixed-slot scheme ----
+// ---- rule 3's sums: [number, sum, sum of squares] of the finite statistics, in fixed slots (slot_sums.h) ----
 
 __global__ __launch_bounds__(256) void stat_sums_kernel(const float* __restrict__ stat, int64_t n, double* __restrict__ part) {
-  __shared__ double wave[4][3];
   double acc[3] = {0.0, 0.0, 0.0};
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const float s = stat[i];
@@ -277,26 +277,7 @@ __global__ __launch_bounds__(256) void stat_sums_kernel(const float* __restrict_
     acc[1] += v;
     acc[2] += v * v;
   }
-  // xor butterflies inside the four wavefronts (a fixed tree; every lane ends with the same bits), then the wavefronts in order
-#pragma unroll
-  for (int k = 0; k < 3; ++k)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) wave[w][k] = acc[k];
-  __syncthreads();
-  if (threadIdx.x < 3) part[(int64_t)blockIdx.x * 3 + threadIdx.x] = ((wave[0][threadIdx.x] + wave[1][threadIdx.x]) + wave[2][threadIdx.x]) + wave[3][threadIdx.x];
-}
-
-// one workgroup: thread k adds slot 0, 1, ... of sum k
-__global__ __launch_bounds__(64) void stat_finish_kernel(const double* __restrict__ part, int slots, double* __restrict__ out) {
-  const int k = threadIdx.x;
-  if (k >= 3) return;
-  double acc = 0.0;
-  for (int s = 0; s < slots; ++s) acc += part[(int64_t)s * 3 + k];
-  out[k] = acc;
+  block_partial<3>(acc, part);
 }
 
 // the checks every entry point over the table shares; 0 or a status
@@ -366,8 +347,8 @@ extern "C" int surf_points_knn_reduce(const float* points, const float* sorted_p
 extern "C" int surf_points_stat_sums(const float* stat, int64_t n, double* partials, double* out, void* stream) {
   if (!partials || !out || n < 0 || (n > 0 && !stat)) return SURF_E_ARG;
   if (n > INT32_MAX) return SURF_E_LIMIT;
-  const int slots = n == 0 ? 0 : (int)((n + 255) / 256 < kSlots ? (n + 255) / 256 : kSlots);
+  const int slots = slots_for(n, kSlots);                            // n == 0: no slots, the finish writes zeros
   if (slots) hipLaunchKernelGGL(stat_sums_kernel, dim3(slots), dim3(256), 0, (hipStream_t)stream, stat, n, partials);
-  hipLaunchKernelGGL(stat_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)partials, slots, out);
+  hipLaunchKernelGGL(slot_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)partials, slots, 3, out);
   return surf_check_launch();
 }

@@ -57,6 +57,7 @@
 #include <float.h>
 #include <math.h>
 
+#include "band.h"              // brick ids and local indices of the brick-major state
 #include "common.h"
 
 namespace {
@@ -80,12 +81,12 @@ struct DenseFetch {
 struct BrickFetch {
   const int32_t* __restrict__ table;
   int nbp;
-  __device__ __forceinline__ int32_t slot(int bx, int by, int bz) const { return table[((int64_t)bx * nbp + by) * nbp + bz]; }
+  __device__ __forceinline__ int32_t slot(int bx, int by, int bz) const { return table[band_brick_id(nbp, bx, by, bz)]; }
   // last / last_slot: the brick of the previous cell and its table entry, kept by the caller - a ray stays in a brick for several
   // cells, and while that brick is missing its cells cost no read at all
   __device__ __forceinline__ bool corners(int i, int j, int k, int64_t pos[8], int64_t& last, int32_t& last_slot) const {
     const int bx = i >> 3, by = j >> 3, bz = k >> 3;
-    const int64_t id = ((int64_t)bx * nbp + by) * nbp + bz;
+    const int64_t id = band_brick_id(nbp, bx, by, bz);
     if (id != last) { last = id; last_slot = table[id]; }
     const int32_t s0 = last_slot;
     if (s0 < 0) return false;                           // the cell's own brick is missing: the cell cannot count
@@ -96,7 +97,7 @@ struct BrickFetch {
       const int cx = x >> 3, cy = y >> 3, cz = z >> 3;
       const int32_t s = (cx == bx && cy == by && cz == bz) ? s0 : slot(cx, cy, cz);     // x <= n - 1: inside the table
       all = all && s >= 0;
-      pos[c] = (int64_t)(s < 0 ? 0 : s) * 512 + (((x & 7) << 6) | ((y & 7) << 3) | (z & 7));
+      pos[c] = (int64_t)(s < 0 ? 0 : s) * 512 + band_local(x, y, z);
     }
     return all;
   }

@@ -1307,6 +1307,32 @@ def _box(points):
     return lo, [b - a for a, b in zip(lo, hi)]
 
 
+def _table_cell_dims(ext, n, floor_cell, max_cells, start_cell=None):
+    """(cell, dims) of a dense cell table over a box of extents `ext` that holds n points.  The cell starts at start_cell or, by
+    default, at about four cells per point by the volume of the padded box, at least floor_cell; it grows by 1.25 until the table
+    has at most max_cells cells.  Pure host arithmetic."""
+    cell = start_cell
+    if cell is None:
+        pad = max(ext) * 1e-3 or 1.0                  # flat or single-point clouds still get a box of some volume
+        vol = (ext[0] + pad) * (ext[1] + pad) * (ext[2] + pad)
+        cell = max((vol / (4.0 * n)) ** (1.0 / 3.0), floor_cell)
+    while True:
+        dims = [int(e // cell) + 1 for e in ext]
+        if dims[0] * dims[1] * dims[2] <= max_cells:
+            return cell, dims
+        cell *= 1.25
+
+
+def _cell_table(points, keys, ncell, tail=False):
+    """(cstart (ncell + 1,) int32, the points in cell order, the sort order) of per-point cell keys: torch's sort, bincount and
+    cumsum.  tail: keys may equal ncell (points that belong to no cell); those sort behind the table and are not counted."""
+    skeys, order = torch.sort(keys)
+    cstart = torch.zeros(ncell + 1, dtype=torch.int32, device=keys.device)
+    counts = torch.bincount(skeys, minlength=ncell + 1)[:ncell] if tail else torch.bincount(skeys, minlength=ncell)
+    cstart[1:] = torch.cumsum(counts, 0)
+    return cstart, points[order].contiguous(), order
+
+
 def mesh_sample_points(vertices, triangles, thresh):
     """dtu_eval.sample_mesh_points on the device: (nv + samples, 3) float64, the vertices followed by the lattice samples of
     every triangle of non-zero area, triangle by triangle.  vertices (nv, 3) float64, triangles (nt, 3) int64.  One host
@@ -1388,20 +1414,10 @@ def nearest_dist_capped(queries, ref, max_dist):
         raise ValueError(f"nearest_dist_capped: {r} reference points exceed int32 indexing")
     L = _lib.lib()
     lo, ext = _box(ref)
-    pad = max(ext) * 1e-3 or 1.0                  # flat or single-point clouds still get a box of some volume
-    vol = (ext[0] + pad) * (ext[1] + pad) * (ext[2] + pad)
-    cell = max((vol / (4.0 * r)) ** (1.0 / 3.0), max(ext) / (THIN_AXIS_CELLS - 2))   # about four cells per reference point
-    while True:
-        dims = [int(e // cell) + 1 for e in ext]
-        if dims[0] * dims[1] * dims[2] <= NEAREST_MAX_CELLS:
-            break
-        cell *= 1.25
+    cell, dims = _table_cell_dims(ext, r, max(ext) / (THIN_AXIS_CELLS - 2), NEAREST_MAX_CELLS)
     keys = torch.empty(r, dtype=torch.int64, device=dev)
     L.surf_dtu_cell_keys(_p(ref), r, lo[0], lo[1], lo[2], cell, dims[0], dims[1], dims[2], _p(keys), _stream())
-    skeys, order = torch.sort(keys)
-    cstart = torch.zeros(dims[0] * dims[1] * dims[2] + 1, dtype=torch.int32, device=dev)
-    cstart[1:] = torch.cumsum(torch.bincount(skeys, minlength=dims[0] * dims[1] * dims[2]), 0)
-    sref = ref[order].contiguous()
+    cstart, sref, _ = _cell_table(ref, keys, dims[0] * dims[1] * dims[2])
     out = torch.empty(m, dtype=torch.float64, device=dev)
     L.surf_dtu_nearest(_p(queries), m, _p(sref), _p(cstart), lo[0], lo[1], lo[2], cell, dims[0], dims[1], dims[2],
                        float(max_dist), _p(out), _stream())
@@ -1478,8 +1494,7 @@ def fscore_voxel_mean(points, voxel):
 
 class NearestTable:
     """The dense cell table of nearest_dist_capped over one reference cloud, kept for several query sets (an ICP round asks the
-    same target twenty times).  cells_per_point / cell / dims say how dense it came out.  The sizing is nearest_dist_capped's,
-    repeated here so that the DTU evaluation's path stays as it is."""
+    same target twenty times).  cells_per_point / cell / dims say how dense it came out."""
 
     def __init__(self, ref):
         _chk_points(ref, "ref")
@@ -1488,21 +1503,11 @@ class NearestTable:
             raise ValueError("NearestTable: empty reference")
         dev = ref.device
         lo, ext = _box(ref)
-        pad = max(ext) * 1e-3 or 1.0                  # flat or single-point clouds still get a box of some volume
-        vol = (ext[0] + pad) * (ext[1] + pad) * (ext[2] + pad)
-        cell = max((vol / (4.0 * r)) ** (1.0 / 3.0), max(ext) / (THIN_AXIS_CELLS - 2))   # about four cells per reference point
-        while True:
-            dims = [int(e // cell) + 1 for e in ext]
-            if dims[0] * dims[1] * dims[2] <= NEAREST_MAX_CELLS:
-                break
-            cell *= 1.25
+        cell, dims = _table_cell_dims(ext, r, max(ext) / (THIN_AXIS_CELLS - 2), NEAREST_MAX_CELLS)
         ncell = dims[0] * dims[1] * dims[2]
         keys = torch.empty(r, dtype=torch.int64, device=dev)
         _lib.lib().surf_dtu_cell_keys(_p(ref), r, lo[0], lo[1], lo[2], cell, dims[0], dims[1], dims[2], _p(keys), _stream())
-        skeys, order = torch.sort(keys)
-        self.cstart = torch.zeros(ncell + 1, dtype=torch.int32, device=dev)
-        self.cstart[1:] = torch.cumsum(torch.bincount(skeys, minlength=ncell), 0)
-        self.sref = ref[order].contiguous()
+        self.cstart, self.sref, order = _cell_table(ref, keys, ncell)
         self.sidx = order.to(torch.int32)
         self.lo, self.cell, self.dims, self.r = lo, cell, dims, r
         self.cells_per_point = ncell / r
@@ -2099,21 +2104,51 @@ def marching_cubes(u, isovalue=0.0, observed_only=False):
 FUSE_MAX_VIEWS = 16                              # SURF_FUSE_MAX_VIEWS: views per launch of surf_fuse_integrate
 
 
-def _chk_fuse_state(tsdf, weight, color, axes):
+def _chk_dense_state(tsdf, weight, color, what):
     _chk(tsdf, torch.float32, "tsdf")
     _chk(weight, torch.float32, "weight")
     if tsdf.dim() != 3 or weight.shape != tsdf.shape:
-        raise ValueError("fuse: tsdf and weight (nx, ny, nz)")
+        raise ValueError(f"{what}: tsdf and weight (nx, ny, nz)")
     if color is not None:
         _chk(color, torch.float32, "color")
         if tuple(color.shape) != tuple(tsdf.shape) + (3,):
-            raise ValueError("fuse: color (nx, ny, nz, 3)")
+            raise ValueError(f"{what}: color (nx, ny, nz, 3)")
+
+
+def _chk_fuse_state(tsdf, weight, color, axes):
+    _chk_dense_state(tsdf, weight, color, "fuse")
     if len(axes) != 3:
         raise ValueError("fuse: three axis arrays")
     for a, n, name in zip(axes, tsdf.shape, ("ax", "ay", "az")):
         _chk(a, torch.float32, name)
         if tuple(a.shape) != (int(n),):
             raise ValueError(f"fuse: {name} holds {tuple(a.shape)} coordinates for {int(n)} lattice points")
+
+
+def _pack_fuse_views(views, color, what):
+    """The host arrays of a launch's view table, (P (n, 12) fp32, hw (n, 2) int32, dscale (n,) fp32, depths, images): images is
+    empty unless colours are fused (color is not None); `what` names the caller in the messages."""
+    n = len(views)
+    P = np.empty((n, 12), dtype=np.float32)
+    hw = np.empty((n, 2), dtype=np.int32)
+    dscale = np.empty(n, dtype=np.float32)
+    depths, images = [], []
+    for v, (Pv, depth, ds, image) in enumerate(views):
+        _chk(depth, torch.float32, f"views[{v}].depth")
+        if depth.dim() != 2:
+            raise ValueError(f"{what}: views[{v}].depth (H, W)")
+        P[v] = np.asarray(Pv, dtype=np.float32).reshape(12)
+        hw[v] = depth.shape
+        dscale[v] = ds
+        depths.append(depth)
+        if color is not None:
+            if image is None:
+                raise ValueError(f"{what}: colours are fused but views[{v}] has no image")
+            _chk(image, torch.float32, f"views[{v}].image")
+            if tuple(image.shape) != tuple(depth.shape) + (3,):
+                raise ValueError(f"{what}: views[{v}].image (H, W, 3)")
+            images.append(image)
+    return P, hw, dscale, depths, images
 
 
 def fuse_integrate(tsdf, weight, color, axes, views, trunc):
@@ -2125,25 +2160,7 @@ def fuse_integrate(tsdf, weight, color, axes, views, trunc):
     n = len(views)
     if n == 0:
         return
-    P = np.empty((n, 12), dtype=np.float32)
-    hw = np.empty((n, 2), dtype=np.int32)
-    dscale = np.empty(n, dtype=np.float32)
-    depths, images = [], []
-    for v, (Pv, depth, ds, image) in enumerate(views):
-        _chk(depth, torch.float32, f"views[{v}].depth")
-        if depth.dim() != 2:
-            raise ValueError(f"fuse_integrate: views[{v}].depth (H, W)")
-        P[v] = np.asarray(Pv, dtype=np.float32).reshape(12)
-        hw[v] = depth.shape
-        dscale[v] = ds
-        depths.append(depth)
-        if color is not None:
-            if image is None:
-                raise ValueError(f"fuse_integrate: colours are fused but views[{v}] has no image")
-            _chk(image, torch.float32, f"views[{v}].image")
-            if tuple(image.shape) != tuple(depth.shape) + (3,):
-                raise ValueError(f"fuse_integrate: views[{v}].image (H, W, 3)")
-            images.append(image)
+    P, hw, dscale, depths, images = _pack_fuse_views(views, color, "fuse_integrate")
     nx, ny, nz = (int(v) for v in tsdf.shape)
     _lib.lib().surf_fuse_integrate(_p(tsdf), _p(weight), _p(color), _p(axes[0]), _p(axes[1]), _p(axes[2]), nx, ny, nz, _np_ptr(P),
                                    _ptr_array(depths), _ptr_array(images) if images else None, _np_ptr(hw), _np_ptr(dscale), n,
@@ -2229,43 +2246,36 @@ def fuse_assign_bricks(mark):
     return table, bricks
 
 
+def _chk_brick_state(tsdf, weight, color, m, what):
+    """Brick-major state of m bricks: tsdf / weight (m * 512,) and color (m * 512, 3) or None."""
+    _chk(tsdf, torch.float32, "tsdf")
+    _chk(weight, torch.float32, "weight")
+    if tsdf.numel() != m * 512 or weight.numel() != m * 512:
+        raise ValueError(f"{what}: tsdf and weight hold 512 points per brick")
+    if color is not None:
+        _chk(color, torch.float32, "color")
+        if color.numel() != m * 512 * 3:
+            raise ValueError(f"{what}: color holds 512 x 3 values per brick")
+
+
+def _chk_brick_table(table, shape, what):
+    _chk(table, torch.int32, "table")
+    if table.numel() != fuse_brick_dims(shape)[1] ** 3:
+        raise ValueError(f"{what}: table holds one entry per brick")
+
+
 def fuse_integrate_bricks(tsdf, weight, color, bricks, axes, views, trunc):
     """fuse_integrate on brick-major state: tsdf / weight (n_slots * 512,) and color (n_slots * 512, 3) or None are updated in
     place with `views` (fuse_integrate's tuples, at most FUSE_MAX_VIEWS, in order) at every lattice point of the listed bricks;
     points past the upper faces are never updated.  The per-point arithmetic is fuse.hip's."""
     nx, ny, nz = _chk_fuse_axes(axes)
     _chk(bricks, torch.int32, "bricks")
-    _chk(tsdf, torch.float32, "tsdf")
-    _chk(weight, torch.float32, "weight")
     m = int(bricks.shape[0])
-    if tsdf.numel() != m * 512 or weight.numel() != m * 512:
-        raise ValueError("fuse_integrate_bricks: tsdf and weight hold 512 points per brick")
-    if color is not None:
-        _chk(color, torch.float32, "color")
-        if color.numel() != m * 512 * 3:
-            raise ValueError("fuse_integrate_bricks: color holds 512 x 3 values per brick")
+    _chk_brick_state(tsdf, weight, color, m, "fuse_integrate_bricks")
     n = len(views)
     if n == 0 or m == 0:
         return
-    P = np.empty((n, 12), dtype=np.float32)
-    hw = np.empty((n, 2), dtype=np.int32)
-    dscale = np.empty(n, dtype=np.float32)
-    depths, images = [], []
-    for v, (Pv, depth, ds, image) in enumerate(views):
-        _chk(depth, torch.float32, f"views[{v}].depth")
-        if depth.dim() != 2:
-            raise ValueError(f"fuse_integrate_bricks: views[{v}].depth (H, W)")
-        P[v] = np.asarray(Pv, dtype=np.float32).reshape(12)
-        hw[v] = depth.shape
-        dscale[v] = ds
-        depths.append(depth)
-        if color is not None:
-            if image is None:
-                raise ValueError(f"fuse_integrate_bricks: colours are fused but views[{v}] has no image")
-            _chk(image, torch.float32, f"views[{v}].image")
-            if tuple(image.shape) != tuple(depth.shape) + (3,):
-                raise ValueError(f"fuse_integrate_bricks: views[{v}].image (H, W, 3)")
-            images.append(image)
+    P, hw, dscale, depths, images = _pack_fuse_views(views, color, "fuse_integrate_bricks")
     _lib.lib().surf_fuse_integrate_bricks(_p(tsdf), _p(weight), _p(color), _p(bricks), m, _p(axes[0]), _p(axes[1]), _p(axes[2]), nx,
                                           ny, nz, _np_ptr(P), _ptr_array(depths), _ptr_array(images) if images else None,
                                           _np_ptr(hw), _np_ptr(dscale), n, ctypes.c_float(float(trunc)), _stream())
@@ -2284,8 +2294,7 @@ def fuse_vertex_colors_bricks(vertices, color, table, shape):
     if vertices.dim() != 2 or vertices.shape[1] != 3 or color.dim() != 2 or color.shape[1] != 3:
         raise ValueError("fuse_vertex_colors_bricks: vertices (V, 3), color (n_slots * 512, 3)")
     nx, ny, nz = (int(v) for v in shape)
-    if table.numel() != fuse_brick_dims(shape)[1] ** 3:
-        raise ValueError("fuse_vertex_colors_bricks: table holds one entry per brick")
+    _chk_brick_table(table, shape, "fuse_vertex_colors_bricks")
     n = int(vertices.shape[0])
     out = torch.empty(n, 3, dtype=torch.uint8, device=vertices.device)
     if n:
@@ -2309,14 +2318,7 @@ def fuse_ray_cast(tsdf, weight, color, lift, hw, z_min=0.0, level=0.0, normals=T
     """The dense state tsdf / weight (nx, ny, nz) (and color (nx, ny, nz, 3) or None) of a UNIFORM lattice seen from one camera:
     (depth (H, W), normal (H, W, 3) or None, color (H, W, 3) or None) fp32 device tensors.  lift: fusion.ray_lift(P, lo, voxel)
     (12 fp32 on the host, lattice-index units); level = -isovalue.  The rule is written out in ray_cast.hip's header comment."""
-    _chk(tsdf, torch.float32, "tsdf")
-    _chk(weight, torch.float32, "weight")
-    if tsdf.dim() != 3 or weight.shape != tsdf.shape:
-        raise ValueError("fuse_ray_cast: tsdf and weight (nx, ny, nz)")
-    if color is not None:
-        _chk(color, torch.float32, "color")
-        if tuple(color.shape) != tuple(tsdf.shape) + (3,):
-            raise ValueError("fuse_ray_cast: color (nx, ny, nz, 3)")
+    _chk_dense_state(tsdf, weight, color, "fuse_ray_cast")
     lift = np.ascontiguousarray(np.asarray(lift, dtype=np.float32).reshape(12))
     H, W, depth, normal, out_color = _ray_cast_outputs(hw, color, normals, tsdf.device)
     nx, ny, nz = (int(v) for v in tsdf.shape)
@@ -2329,18 +2331,10 @@ def fuse_ray_cast_bricks(tsdf, weight, color, table, shape, lift, hw, z_min=0.0,
     """fuse_ray_cast on brick-major state (tsdf / weight (n_slots * 512,), color (n_slots * 512, 3) or None) of the lattice `shape`,
     read through the brick table: a corner in a brick that is not allocated is unobserved.  Equal arrays."""
     _chk(tsdf, torch.float32, "tsdf")
-    _chk(weight, torch.float32, "weight")
-    _chk(table, torch.int32, "table")
     m = tsdf.numel() // 512
-    if tsdf.numel() != m * 512 or weight.numel() != m * 512:
-        raise ValueError("fuse_ray_cast_bricks: tsdf and weight hold 512 points per brick")
-    if color is not None:
-        _chk(color, torch.float32, "color")
-        if color.numel() != m * 512 * 3:
-            raise ValueError("fuse_ray_cast_bricks: color holds 512 x 3 values per brick")
+    _chk_brick_state(tsdf, weight, color, m, "fuse_ray_cast_bricks")
     nx, ny, nz = (int(v) for v in shape)
-    if table.numel() != fuse_brick_dims(shape)[1] ** 3:
-        raise ValueError("fuse_ray_cast_bricks: table holds one entry per brick")
+    _chk_brick_table(table, shape, "fuse_ray_cast_bricks")
     lift = np.ascontiguousarray(np.asarray(lift, dtype=np.float32).reshape(12))
     H, W, depth, normal, out_color = _ray_cast_outputs(hw, color, normals, table.device)
     if m == 0:                                                     # nothing allocated: nothing is observed, no ray hits
@@ -3136,26 +3130,17 @@ class PointKnnTable:
             lo, hi = [0.0, 0.0, 0.0], [0.0, 0.0, 0.0]
         del finite
         ext = [b - a for a, b in zip(lo, hi)]
-        if cell is None:
-            pad = max(ext) * 1e-3 or 1.0              # flat or single-point clouds still get a box of some volume
-            vol = (ext[0] + pad) * (ext[1] + pad) * (ext[2] + pad)
-            cell = max((vol / (4.0 * n)) ** (1.0 / 3.0), float(max_dist) / 16.0)
-        cell = float(cell)
+        if cell is not None:
+            cell = float(cell)
+        if cell is None or cell > 0:                  # (a given cell that is NaN or <= 0 has no table: the check below raises)
+            cell, dims = _table_cell_dims(ext, n, float(max_dist) / 16.0, POINTS_KNN_MAX_CELLS, cell)
         if not (cell > 0 and np.isfinite(cell)):
             raise ValueError(f"PointKnnTable: cell must be finite and > 0, got {cell}")
-        while True:
-            dims = [int(e // cell) + 1 for e in ext]
-            if dims[0] * dims[1] * dims[2] <= POINTS_KNN_MAX_CELLS:
-                break
-            cell *= 1.25
         ncell = dims[0] * dims[1] * dims[2]
         keys = torch.empty(n, dtype=torch.int64, device=dev)
         _lib.lib().surf_points_knn_keys(_p(points), n, lo[0], lo[1], lo[2], cell, dims[0], dims[1], dims[2], _p(keys), _stream())
-        skeys, order = torch.sort(keys)
-        self.cstart = torch.zeros(ncell + 1, dtype=torch.int32, device=dev)
-        self.cstart[1:] = torch.cumsum(torch.bincount(skeys, minlength=ncell + 1)[:ncell], 0)
+        self.cstart, self.spts, order = _cell_table(points, keys, ncell, tail=True)
         self.points = points
-        self.spts = points[order].contiguous()
         self.sidx = order.to(torch.int32)
         self.lo, self.cell, self.dims, self.n = lo, cell, dims, n
         self.cells_per_point = ncell / n

@@ -121,6 +121,48 @@ def test_nearest_empty_and_ties():
     assert (d == 0).all() and np.array_equal(i, np.minimum(64 - np.arange(65), 65 + np.arange(65)))
 
 
+@pytest.mark.parametrize("r", [1, 7, 300])
+def test_nearest_distance_and_index_walks_agree(r):
+    """The two instances of the one shell walk: nearest_dist_capped's distances equal nearest_capped_index's bit for bit, and the
+    index attains that distance and is the smallest that does.  All coordinates lie on a 0.125 lattice, so squared distances are
+    exact and tie exactly.  257 queries (one past a block): copies of reference points, the midpoint of two reference points that
+    no other one is nearer to, two far outside the grid, one NaN, the rest scattered over the box and around it."""
+    rng = np.random.default_rng(r)
+    ref = rng.integers(-8, 9, (r, 3)) * 0.25
+    if r >= 2:
+        ref[0], ref[1] = (10.0, 10.0, 10.0), (10.5, 10.0, 10.0)
+    q = rng.integers(-24, 25, (257, 3)) * 0.125
+    q[:64] = ref[np.arange(64) % r]
+    q[64] = (10.25, 10.0, 10.0)
+    q[65], q[66] = (1.0e6, 0.0, 0.0), (0.25, -1.0e12, 3.0e9)
+    q[67] = (np.nan, 0.0, 0.0)
+    d = q[:, None, :] - ref[None, :, :]
+    d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+    d2[67] = np.inf                                                              # a NaN query has no neighbour
+    best = d2.min(axis=1)
+    assert r == 1 or ((d2 == best[:, None]).sum(axis=1)[64] == 2 and (d2[68:] == best[68:, None]).sum(axis=1).max() >= 2)
+    tq, tref = torch.from_numpy(q).cuda(), torch.from_numpy(ref).cuda()
+
+    def check(tq, d2, max_dist):
+        best = d2.min(axis=1)
+        dist = ops.nearest_dist_capped(tq, tref, max_dist)
+        dist_i, index = ops.nearest_capped_index(tq, tref, max_dist)
+        assert dist.dtype == torch.float64 and torch.equal(dist, dist_i)
+        got_d, got_i = dist_i.cpu().numpy(), index.cpu().numpy()
+        near = np.sqrt(best) < max_dist
+        assert np.array_equal(np.isfinite(got_d), near) and np.isposinf(got_d[~near]).all() and (got_i[~near] == -1).all()
+        assert np.array_equal(bits(got_d[near]), bits(np.sqrt(best[near])))
+        assert np.array_equal(got_i[near], np.argmin(d2[near], axis=1))         # argmin: the first, i.e. smallest, index
+        return near
+
+    near = check(tq, d2, 0.75)
+    assert near[:64].all() and near[64] == (r > 1) and not near[65:68].any() and 0 < near[68:].sum() < 189
+    apart = best > 0                                                             # below the smallest distance: nothing is near
+    assert not check(tq[torch.from_numpy(apart).cuda()].contiguous(), d2[apart], 0.5 * np.sqrt(best[apart].min())).any()
+    near = check(tq, d2, 0.0625)                                                 # with them, only the copies (distance 0) are
+    assert near[:64].all() and not near[64:].any()
+
+
 @pytest.mark.parametrize("offset", H.ICP_OFFSETS)
 def test_icp_recovers_the_motion(offset):
     """The host test's two cases against the same truth and the same bound (not against the host's transform)."""

@@ -383,3 +383,55 @@ def test_status_entry_points_raise_by_themselves():
     for name, (res, _) in _lib.SIGNATURES.items():
         fn = getattr(L, name)
         assert (fn.errcheck is not None) == (res is _lib.ctypes.c_int and name not in _lib.VALUE_RETURNING), name
+
+
+def _parent_table_sizing(ext, n, floor_cell, max_cells, start_cell=None):
+    """The table sizing as nearest_dist_capped, NearestTable and PointKnnTable each wrote it out before they shared
+    ops._table_cell_dims: about four cells per point by the padded box's volume, at least the caller's floor (or the cell the
+    caller gives), grown by 1.25 until the table fits its cap."""
+    cell = start_cell
+    if cell is None:
+        pad = max(ext) * 1e-3 or 1.0
+        vol = (ext[0] + pad) * (ext[1] + pad) * (ext[2] + pad)
+        cell = max((vol / (4.0 * n)) ** (1.0 / 3.0), floor_cell)
+    while True:
+        dims = [int(e // cell) + 1 for e in ext]
+        if dims[0] * dims[1] * dims[2] <= max_cells:
+            break
+        cell *= 1.25
+    return cell, dims
+
+
+@pytest.mark.parametrize("name, ext, n, floor, cap, start, grows", [
+    ("flat", (2.0, 1.0, 0.0), 1000, "thin", "nearest", None, False),
+    ("single point", (0.0, 0.0, 0.0), 1, "thin", "nearest", None, False),
+    ("elongated", (1.0e4, 1.0e-3, 1.0e-3), 5, "thin", "nearest", None, False),            # the 2^21-cells-per-axis floor decides
+    ("dense cube", (1000.0, 1000.0, 1000.0), 10 ** 9, 0.01 / 16.0, "knn", None, True),    # four cells per point exceed the cap
+    ("elongated, small cap", (100.0, 1.0, 1.0), 100000, 0.25 / 16.0, 1000, None, True),
+    ("given cell", (3.0, 2.0, 1.0), 50, 0.5 / 16.0, "knn", 0.5, False),
+    ("given cell, too fine", (3.0, 2.0, 1.0), 50, 0.5 / 16.0, "knn", 1.0e-3, True),
+])
+def test_table_sizing_is_the_three_callers_sizing(name, ext, n, floor, cap, start, grows):
+    """ops._table_cell_dims against the expressions its three callers used to repeat, with each caller's own floor and cap, and
+    against the cap itself.  Host arithmetic only."""
+    from surf_amd import ops
+    floor = max(ext) / (ops.THIN_AXIS_CELLS - 2) if floor == "thin" else floor
+    cap = {"nearest": ops.NEAREST_MAX_CELLS, "knn": ops.POINTS_KNN_MAX_CELLS}.get(cap, cap)
+    cell, dims = ops._table_cell_dims(list(ext), n, floor, cap, start)
+    want_cell, want_dims = _parent_table_sizing(list(ext), n, floor, cap, start)
+    assert cell == want_cell and list(dims) == want_dims
+    assert all(d >= 1 for d in dims) and dims[0] * dims[1] * dims[2] <= cap
+    assert all(d <= ops.THIN_AXIS_CELLS for d in dims)
+    assert all(int(e // cell) == d - 1 for e, d in zip(ext, dims))                         # the last cell holds the box's far face
+    if start is None:
+        assert cell >= floor
+    first = start
+    if first is None:
+        pad = max(ext) * 1e-3 or 1.0
+        first = max(((ext[0] + pad) * (ext[1] + pad) * (ext[2] + pad) / (4.0 * n)) ** (1.0 / 3.0), floor)
+    assert (cell > first) == grows
+    if grows:                                                                               # the smallest growth that fits
+        fine = [int(e // (cell / 1.25)) + 1 for e in ext]
+        assert fine[0] * fine[1] * fine[2] > cap
+    else:
+        assert cell == first
