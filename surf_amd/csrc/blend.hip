@@ -344,7 +344,11 @@ __global__ __launch_bounds__(256, (NS <= 2 ? 2 : 1)) void blend_kernel(BlendArgs
       f32x4 tC = tap_finish(qC[v]);
       if (h != 0) tC = f32x4{0.f, 0.f, 0.f, 0.f};
       bool ok = okv[v];
-      ok = ok && (__shfl_xor((int)ok, 32) != 0);  // AND over all four levels
+      // AND over all four levels.  The exchange runs in EVERY lane, outside the `&&`: behind it a lane whose own half is
+      // outside would skip the shuffle, and the half that is inside would read the idle lane's register (seen: a point inside
+      // levels 0, 1 and outside level 2 or 3 of a floored pyramid counted as valid)
+      const int ok_other = __shfl_xor((int)ok, 32);
+      ok = ok & (ok_other != 0);
       mk[v] = ok ? 1.f : 0.f;
       nvalid += ok ? 1 : 0;
       rgb[v][0] = tC[0]; rgb[v][1] = tC[1]; rgb[v][2] = tC[2];
@@ -674,6 +678,7 @@ extern "C" int surf_blend(const float* pts, const uint8_t* mask, const int32_t* 
     a.feats[l] = h_feats[l];
     a.hw[2 * l] = h_hw[2 * l];
     a.hw[2 * l + 1] = h_hw[2 * l + 1];
+    if (h_hw[2 * l] < 2 || h_hw[2 * l + 1] < 2) return SURF_E_LIMIT;  // (W - 1) / 2 divides the texel coordinate (as surf_blend_split)
   }
   for (int v = 0; v < SURF_MAX_VIEWS; ++v) {
     const int s = v < nv ? v : 0;

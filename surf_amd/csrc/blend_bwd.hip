@@ -421,6 +421,7 @@ extern "C" int surf_blend_backward(const float* pts, const int32_t* idx, int64_t
     a.feats[l] = h_feats_t4[l];
     a.hw[2 * l] = h_feat_hw[2 * l];
     a.hw[2 * l + 1] = h_feat_hw[2 * l + 1];
+    if (h_feat_hw[2 * l] < 2 || h_feat_hw[2 * l + 1] < 2) return SURF_E_LIMIT;  // (W - 1) / 2 divides the texel coordinate (as surf_blend_split)
     a.gfeats[l] = h_gfeats_t4 ? h_gfeats_t4[l] : nullptr;
     if (h_gfeats_t4 && !h_gfeats_t4[l]) return SURF_E_ARG;
   }

@@ -482,7 +482,7 @@ template <class P> constexpr int lds_bytes() { return image_bytes<P::BB>(); }
 
 // Per-wavefront staging slot in global memory (L2 / Infinity-Cache resident: written in pass 1, read back within the
 // same tile): per source view five 16-byte groups per lane = [floc 0..3][floc 4..7][floc 8..11][ray_diff][rgb, +-ex]
-// (ex = exp(|s| (dot - 1)) > 0, stored negated where the view's mask is 0).  It makes the register state independent of
+// (ex = exp(|s| (dot - 1)) >= 0, stored with the sign bit set where the view's mask is 0).  It makes the register state independent of
 // the number of views, so the view loops are real loops: one code path for 1..7 source views, ~4x less code than the
 // unrolled form and no spills at two wavefronts per SIMD.
 constexpr int SLOT_GROUPS = 5;
@@ -509,7 +509,7 @@ struct ViewState {
   float floc[12];
   float rd[4];
   float rgb[3];
-  float ex;  // > 0; mk = 1
+  float ex;  // >= 0 (zero once |s| (1 - dot) passes ~87)
   float mk;
 };
 // (v is wave-uniform: a scalar branch; the two address spaces get their own instructions - a pointer select would make
@@ -520,7 +520,8 @@ __device__ __forceinline__ void slot_store_at(PtrT p, const ViewState& s, int st
   p[1 * stride] = f32x4{s.floc[4], s.floc[5], s.floc[6], s.floc[7]};
   p[2 * stride] = f32x4{s.floc[8], s.floc[9], s.floc[10], s.floc[11]};
   p[3 * stride] = f32x4{s.rd[0], s.rd[1], s.rd[2], s.rd[3]};
-  p[4 * stride] = f32x4{s.rgb[0], s.rgb[1], s.rgb[2], s.mk != 0.f ? s.ex : -s.ex};
+  // the mask travels in the SIGN BIT of ex (ex >= 0): -0.f for a masked view whose ex underflowed, +0.f for a valid one
+  p[4 * stride] = f32x4{s.rgb[0], s.rgb[1], s.rgb[2], __uint_as_float(__float_as_uint(s.ex) | (s.mk != 0.f ? 0u : 0x80000000u))};
 }
 template <class PtrT>
 __device__ __forceinline__ void slot_load_at(PtrT p, ViewState& s, int stride = 64) {
@@ -533,7 +534,7 @@ __device__ __forceinline__ void slot_load_at(PtrT p, ViewState& s, int stride = 
   }
   s.rd[0] = x[3][0]; s.rd[1] = x[3][1]; s.rd[2] = x[3][2]; s.rd[3] = x[3][3];
   s.rgb[0] = x[4][0]; s.rgb[1] = x[4][1]; s.rgb[2] = x[4][2];
-  s.mk = x[4][3] > 0.f ? 1.f : 0.f;
+  s.mk = (__float_as_uint(x[4][3]) >> 31) == 0u ? 1.f : 0.f;  // not `> 0`: a valid view's ex may be +0 (|s| (1 - dot) > 87)
   s.ex = fabsf(x[4][3]);
 }
 typedef __attribute__((address_space(3))) f32x4* lds_f32x4_ptr;
@@ -680,7 +681,11 @@ __device__ __forceinline__ bool pass1_finish(const Ctx& c, const Geo& geo, float
   const f32x4 tA = tap_finish(qA, gA), tB = tap_finish(qB, gB);
   f32x4 tC = tap_finish(qC, gA);
   if (h != 0) tC = f32x4{0.f, 0.f, 0.f, 0.f};
-  ok = ok && (__shfl_xor((int)ok, 32) != 0);  // AND over all four levels
+  // AND over all four levels.  The exchange runs in EVERY lane, outside the `&&`: behind it a lane whose own half is outside
+  // would skip the shuffle, and the half that is inside would read the idle lane's register (seen: a point inside levels 0, 1
+  // and outside level 2 or 3 of a floored pyramid counted as valid)
+  const int ok_other = __shfl_xor((int)ok, 32);
+  ok = ok & (ok_other != 0);
   st.mk = ok ? 1.f : 0.f;
   st.rgb[0] = tC[0]; st.rgb[1] = tC[1]; st.rgb[2] = tC[2];
   // local channel order: half 0 = [rgb, F0, F1], half 1 = [F2, F3, 0, 0, 0]

@@ -773,15 +773,30 @@ _BLEND_LAYERS = [  # (state_dict prefix, in, out, IN column, ADJ column) of surf
     ("rgb_fc.0", 37, 16, 498, 535), ("rgb_fc.2", 16, 8, 551, 567), ("rgb_fc.4", 8, 1, 575, 583)]
 
 
+def _check_blend_maps(feats_t4, imgs_t4, cams, gfeats_t4=None):
+    """The blend kernels index the source images with the finest level's height and width and every map with cams.nv views,
+    and take exactly four levels: anything else would read out of bounds, so it is refused before a launch."""
+    if len(feats_t4) != 4:
+        raise ValueError(f"blend: {len(feats_t4)} feature levels, the kernels take 4")
+    for l, f in enumerate(feats_t4):
+        if f.dim() != 4 or f.shape[3] != 4 or f.shape[0] != cams.nv:
+            raise ValueError(f"blend: feature level {l} has shape {tuple(f.shape)}, expected ({cams.nv}, H, W, 4)")
+    if tuple(imgs_t4.shape) != tuple(feats_t4[0].shape):
+        raise ValueError(f"blend: imgs_t4 has shape {tuple(imgs_t4.shape)}, the finest feature level {tuple(feats_t4[0].shape)}")
+    if gfeats_t4 is not None and [tuple(g.shape) for g in gfeats_t4] != [tuple(f.shape) for f in feats_t4]:
+        raise ValueError("blend: gfeats_t4 must have the shapes of feats_t4")
+
+
 def blend_backward(pts, active_idx, gcolor, feats_t4, imgs_t4, cams, raw_weights, want_color=False, gfeats_t4=None):
     """Gradients of sum_n gcolor_n . colour_n w.r.t. the blending network's parameters (surf_blend_backward; the batch
     reductions are surf_colgram_p: matrix cores).  raw_weights: device tensor of blend_raw_weights(sd) (packing.blend_raw_device).
     gfeats_t4: four texel4 maps shaped like feats_t4 that accumulate the gradient of the sampled feature channels.
     Returns {state_dict name: gradient} (+ "_color": the recomputed colours of the active samples, if asked)."""
+    _check_blend_maps(feats_t4, imgs_t4, cams, gfeats_t4)
     _chk(pts, torch.float32, "pts")
     _chk(gcolor, torch.float32, "gcolor")
     _chk(raw_weights, torch.float32, "raw weights")
-    assert len(feats_t4) == 4 and gcolor.shape[0] == pts.shape[0]
+    assert gcolor.shape[0] == pts.shape[0]
     dev = pts.device
     n = int(active_idx.shape[0]) if active_idx is not None else pts.shape[0]
     V = cams.nv - 1
@@ -824,6 +839,7 @@ class Cameras:
 def blend(pts, feats_t4, imgs_t4, cams, packed, mask=None, compact_active=True, active_idx=None, active_count=None):
     """projector.py:501-556 + blending_network.py:69-118.  feats_t4: list fine -> coarse of (nv,H,W,4).
     Returns (color (n,3), n_valid (n) uint8); masked-out rows are zero."""
+    _check_blend_maps(feats_t4, imgs_t4, cams)
     _chk(pts, torch.float32, "pts")
     n = pts.shape[0]
     dev = pts.device
