@@ -1209,6 +1209,75 @@ int surf_points_knn_reduce(const float* points, const float* sorted_points, cons
                            float* normal, void* stream);
 int surf_points_stat_sums(const float* stat, int64_t n, double* partials, double* out, void* stream);
 
+/*
+ * Point-set surface: a signed distance on the lattice nodes near an ORIENTED point cloud, from which the fusion path's marching
+ * cubes, vertex colours, ray casting and simplification take a mesh (surf_amd/point_surface.py, backend="device";
+ * point_surface.hip).  Added under SURF_ABI_VERSION 41 without a bump, like the entry points above.  The field is Kolluri's
+ * implicit moving-least-squares surface, f(x) = sum_i w_i(x) n_i . (x - p_i) / sum_i w_i(x), with the compact weight
+ * w = (1 - |x - p|^2 / R^2)^4: one gather pass, no global solve, only + - * / and comparisons, so the device path returns the host
+ * path's arrays.  fp32 with separate multiplies and adds (-ffp-contract=off) in the stated order unless fp64 is named.
+ *
+ * THE RULE.  P (n,3) fp32 world points, N (n,3) fp32 normals pointing into free space (used as given, not renormalised), optional
+ * colours (n,3) uint8, n <= 2^31 - 1.  A uniform lattice in the fusion conventions: fp32 axis arrays ax (nx), ay (ny), az (nz) that
+ * follow lo + voxel * i (lo, voxel fp64: fusion.uniform_lattice) and the band layout above: res = max(nx,ny,nz) <= SURF_BAND_MAX_RES,
+ * nbp = ceil(res / 8), brick ids (bx nbp + by) nbp + bz, state brick-major, slot * 512 + (lx << 6 | ly << 3 | lz).  A support radius R
+ * (fp32, world units, R and R * R finite and > 0) and min_points >= 1.
+ *   reach (fp64, lattice steps) comes from the caller and is the same number in every call:
+ *        reach = (R / voxel) * (1 + 1e-5) + 4 * ulp32(A) / voxel,   A = the largest |axis value|,
+ *      where ulp32(A) is the spacing of fp32 at A.  It bounds |i - u| of every admitted (node i, point at lattice coordinate u) pair
+ *      per axis: an axis value lies within 2 ulp32(A) of lo + voxel * i (uniform_lattice's tolerance), the fp32 rounding of dx and of
+ *      d2 moves the admission boundary by less than 1e-6 R, and the fp64 rounding of u is below 1e-12.  ring = ceil(reach / 8) is
+ *      the number of bricks the support reaches across; 1 <= ring <= SURF_CLOUD_MAX_RING (SURF_E_LIMIT beyond: R just under 32 voxels).
+ *   1. taking part.  A point takes part iff its three coordinates and its three normal components are finite and the normal is not
+ *      (0,0,0) (estimate_normals returns that for a starved point) - and rule 2 keeps it.
+ *   2. brick of a point.  Per axis u = ((double)p - lo) / voxel and b = floor(u / 8) (the division by 8 is exact), in fp64; b may be
+ *      negative or >= the bricks of the axis, ceil(n_axis / 8): a point beyond the lattice still reaches nodes inside it.  A point
+ *      with b < -ring or b >= ceil(n_axis / 8) + ring on any axis takes no part (by the bound above it is admitted at no node).
+ *   3. order.  A node's sums run over the points taking part in ascending (bx, by, bz, caller index) order: the order of the
+ *      composite keys below, which the lattice defines and no tunable cell does.  The keys are unique, so any sort gives it.
+ *   4. per node x = (ax[i], ay[j], az[k]) and point, in fp32:  dx = x - p.x (dy, dz alike);  d2 = (dx*dx + dy*dy) + dz*dz;  the point is
+ *      ADMITTED iff d2 < R2, with R2 = R * R and inv = 1 / R2 formed once;  t = 1 - d2 * inv;  t2 = t * t;  w = t2 * t2;
+ *      g = (dx*nx + dy*ny) + dz*nz;  then count += 1, sw += w, sf += w * g and per channel sc += w * c with c = (colour + 0.5) / 256
+ *      (exact in fp32; the inverse of fusion.quantise_colors_host).  The sums are sequential fp32 from +0.  (A pair that is not
+ *      admitted may add +0 instead: that leaves such a sum as it is.)
+ *   5. node state, in fusion's conventions.  Observed iff count >= min_points and sw > 0:  tsdf = fmin(fmax((sf / sw) / R, -1), 1),
+ *      weight = (float)count, color = sc / sw per channel.  Not observed, or past the upper faces of the lattice (i >= nx ...):
+ *      tsdf = weight = color = 0.  tsdf is positive on the normals' side, as in front of a measured surface; u = -tsdf through
+ *      surf_fuse_lattice.
+ *   6. allocation.  Per axis a point can be admitted at the nodes i0 = ceil(u - reach) .. i1 = floor(u + reach) only (fp64, then
+ *      integers), clamped to [0, n_axis - 1]; a point with an empty interval on some axis allocates nothing.  Allocated are the
+ *      bricks (i0 >> 3 .. i1 >> 3) per axis, a box of bricks per point: a superset of the bricks that hold a node with count >= 1,
+ *      and for R = 3 voxels about 5 bricks per point where the blanket (2 ring + 1)^3 neighbourhood has 27.  The mesh does not
+ *      depend on the allocation: a node outside it is unobserved, as a node with count 0 is.
+ *
+ * Entry points, in the order surf_amd.ops calls them (the sort and the gathers between them are the caller's):
+ *   surf_cloud_brick_keys: keys (n) int64 = (key << 31) | index, key = ((bx + ring) * ey + (by + ring)) * ez + (bz + ring) over the
+ *     extended brick grid e_axis = ceil(n_axis / 8) + 2 ring, or key = ex * ey * ez for a point that takes no part: those sort
+ *     behind every brick, as the tail of surf_points_knn_keys does.
+ *   surf_cloud_mark_bricks: rule 6 over sorted_points (m,3), the points taking part in key order; mark (nbp^3 bytes) gets a 1 at
+ *     every allocated brick.  surf_compact and surf_band_assign turn the marks into the table and the brick list.
+ *   surf_cloud_field_bricks: rules 3-5 at the 512 nodes of every listed brick; every value of tsdf, weight (n_bricks * 512) and,
+ *     given together with sorted_colors or not at all (SURF_E_ARG otherwise), color (n_bricks * 512, 3) is written.  sorted_keys
+ *     (m), sorted_points, sorted_normals (m,3) fp32 and sorted_colors (m,3) uint8: the points taking part in ascending key order.
+ *     One workgroup per brick; the candidates of a brick are the points of the (2 ring + 1)^3 bricks around it, found as
+ *     (2 ring + 1)^2 runs of the sorted keys by binary search (no start table) and staged through LDS in key order; a candidate
+ *     whose rule-6 box misses the brick is dropped while staging - it is admitted at none of its nodes.  staged (n_bricks) int32, or
+ *     null: the candidates of every brick that were not dropped (a brick evaluates 512 x staged pairs).
+ * n == 0 (keys), m == 0 (mark) and n_bricks == 0 (field) return 0 without a launch; m == 0 with bricks writes zero state.
+ * !(voxel > 0), a reach that is not finite and > 0, min_points < 1, an R that is not finite and > 0 (or whose square is 0 or not
+ * finite) are SURF_E_ARG; res > SURF_BAND_MAX_RES, ring > SURF_CLOUD_MAX_RING, n or m >= 2^31, n_bricks * 512 >= 2^31 are SURF_E_LIMIT.
+ */
+#define SURF_CLOUD_MAX_RING 4
+int surf_cloud_brick_keys(const float* points, const float* normals, int64_t n, double lo_x, double lo_y, double lo_z, double voxel,
+                          int64_t nx, int64_t ny, int64_t nz, double reach, int64_t* keys, void* stream);
+int surf_cloud_mark_bricks(const float* sorted_points, int64_t m, double lo_x, double lo_y, double lo_z, double voxel, int64_t nx,
+                           int64_t ny, int64_t nz, double reach, uint8_t* mark, void* stream);
+int surf_cloud_field_bricks(const int64_t* sorted_keys, const float* sorted_points, const float* sorted_normals,
+                            const uint8_t* sorted_colors, int64_t m, const int32_t* bricks, int64_t n_bricks, const float* ax,
+                            const float* ay, const float* az, int64_t nx, int64_t ny, int64_t nz, double lo_x, double lo_y,
+                            double lo_z, double voxel, double reach, float radius, int min_points, float* tsdf, float* weight,
+                            float* color, int32_t* staged, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,10 @@ With --cloud_outliers K STD_RATIO (or --cloud_radius_outliers MIN_NEIGHBOURS) an
 (surf_amd/point_filter.py, csrc/point_knn.hip: k nearest neighbours within --cloud_max_dist): statistical (or radius) outlier
 removal first, then normals on what is left, turned towards the camera that saw each point; the filtered cloud is what goes to
 <N>_points.ply (with nx ny nz) and to the scores, and the record gains `cloud_filter` and `cloud_normals`.
+With --cloud_mesh [--cloud_mesh_radius VOXELS] [--cloud_mesh_min_points N] (needs --point_cloud and --cloud_normals) the oriented
+cloud is then meshed itself: a point-set surface on the same lattice (surf_amd/point_surface.py, csrc/point_surface.hip), simplified
+by --simplify_mm -> <N>_cloud_mesh.ply; the record gains `cloud_mesh` {radius, min_points, points, bricks, allocated_share, vertices,
+faces, file, ms} and, with --eval_dir / --tnt_dir, that mesh's scores inside it.
 
 The lattice covers the union of the groups' normalised [-1, 1]^3 boxes (fusion.bounds_from_scale_mats; a first pass over the items
 reads their scale_mats) at --voxel_mm world units per step, or --resolution points along the longest side.
@@ -93,6 +97,13 @@ def parse_args(argv=None):
     ap.add_argument("--cloud_max_dist", type=float, default=None,
                     help="search radius of the three cloud steps in world units (default: 10 lattice steps; a guess - the record's "
                          "`starved` count says when it is too small)")
+    ap.add_argument("--cloud_mesh", action="store_true",
+                    help="with --point_cloud and --cloud_normals: also mesh the oriented cloud itself, a point-set surface on the "
+                         "--voxel_mm lattice (surf_amd/point_surface.py, csrc/point_surface.hip) -> <name>_cloud_mesh.ply, simplified "
+                         "by --simplify_mm and scored like the mesh")
+    ap.add_argument("--cloud_mesh_radius", type=float, default=3.0, metavar="VOXELS", help="support radius of --cloud_mesh in lattice steps")
+    ap.add_argument("--cloud_mesh_min_points", type=int, default=4, metavar="N",
+                    help="--cloud_mesh: a lattice point is observed with at least N points inside the radius")
     ap.add_argument("--clean_mesh", action="store_true",
                     help="the DTU evaluation protocol's cleaner on the world-frame mesh (evaluation/clean_dtu.py; needs --dtu_test_dir)")
     ap.add_argument("--dtu_test_dir", default=None, help="DTU_TEST tree (cameras/, scan<N>/mask/) of --clean_mesh")
@@ -154,6 +165,10 @@ def run(args, state=None):
         raise SystemExit("fuse_scene: --cloud_outliers, --cloud_radius_outliers and --cloud_normals need --point_cloud")
     if cloud_outliers is not None and cloud_radius is not None:
         raise SystemExit("fuse_scene: one of --cloud_outliers and --cloud_radius_outliers")
+    cloud_mesh = bool(getattr(args, "cloud_mesh", False))
+    cloud_mesh_record = None
+    if cloud_mesh and not (args.point_cloud and cloud_normals is not None):
+        raise SystemExit("fuse_scene: --cloud_mesh needs --point_cloud and --cloud_normals (the surface is taken from oriented points)")
     cfg = C.parse_file(args.conf)
     dconf = cfg["val_dataset"]
     if args.data_dir is not None:
@@ -241,6 +256,22 @@ def run(args, state=None):
             cloud, cloud_nrm, cloud_records = point_filter.clean_step(cloud, cloud_views, outliers=ratio, radius_outliers=cloud_radius,
                                                                       normals_k=cloud_normals, max_dist=max_dist, device=dev)
             mesh_io.write_ply_points(points_path, cloud.points, cloud.colors, normals=cloud_nrm)
+            if cloud_mesh:
+                # ---- the oriented cloud as a surface of its own: a point-set surface on the fusion lattice ----
+                from surf_amd import point_surface
+                t0 = time.perf_counter()
+                st = {}
+                radius = float(getattr(args, "cloud_mesh_radius", 3.0)) * voxel
+                min_points = int(getattr(args, "cloud_mesh_min_points", 4))
+                cm = point_surface.reconstruct(cloud, cloud_nrm, voxel, radius=radius, min_points=min_points, bounds=(lo, hi),
+                                               simplify_cell=args.simplify_mm, device=dev, stats=st)
+                if len(cm[1]) == 0:
+                    raise SystemExit("fuse_scene: --cloud_mesh found no zero crossing between observed lattice points (empty mesh)")
+                cloud_mesh_path = os.path.join(args.out_dir, "meshes", "fused", f"{name}_cloud_mesh.ply")
+                mesh_io.write_ply(cloud_mesh_path, cm[0], cm[1], colors=cm[2] if len(cm) > 2 else None)
+                cloud_mesh_record = {"radius": radius, "min_points": min_points, "points": st["points"], "bricks": st["bricks"],
+                                     "allocated_share": st["allocated_share"], "vertices": st["vertices"], "faces": st["faces"],
+                                     "file": cloud_mesh_path, "ms": 1e3 * (time.perf_counter() - t0)}
         else:
             mesh_io.write_ply_points(points_path, cloud.points, cloud.colors)
         cloud_views.clear()
@@ -295,6 +326,8 @@ def run(args, state=None):
         state.update(model=model, volume=volume, vertices=v, triangles=t, colors=colors)
         if cloud is not None:
             state.update(cloud=cloud)
+        if cloud_mesh_record is not None:
+            state.update(cloud_mesh=cm)
     model_residual = None
     if render_dir is not None:
         # ---- the fused model seen from every fused view's camera: no mesh involved, one kernel launch and one copy per view ----
@@ -333,6 +366,8 @@ def run(args, state=None):
     if cloud is not None:
         rec.update(points=int(len(cloud.points)), points_file=points_path)
         rec.update(cloud_records)                       # cloud_filter / cloud_normals: without the flags the record is what it was
+    if cloud_mesh_record is not None:                   # without the flag the record is what it was
+        rec.update(cloud_mesh=cloud_mesh_record)
     if args.eval_dir is not None:
         t0 = time.perf_counter()
         d2s, s2d, overall = dtu_eval.evaluate_scan(mesh_path, args.eval_dir, args.scan, patch_size=args.patch_size,
@@ -347,6 +382,13 @@ def run(args, state=None):
                                                        rng=np.random.default_rng(args.shuffle_seed), device=args.eval_device)
             ms["evaluate_points"] = 1e3 * (time.perf_counter() - t0)
             rec.update(pcd_d2s=d2s, pcd_s2d=s2d, pcd_chamfer=overall)
+        if cloud_mesh_record is not None:
+            t0 = time.perf_counter()
+            d2s, s2d, overall = dtu_eval.evaluate_scan(cloud_mesh_record["file"], args.eval_dir, args.scan, patch_size=args.patch_size,
+                                                       max_dist=args.max_dist, downsample_density=args.downsample_density,
+                                                       rng=np.random.default_rng(args.shuffle_seed), device=args.eval_device)
+            ms["evaluate_cloud_mesh"] = 1e3 * (time.perf_counter() - t0)
+            cloud_mesh_record.update(d2s=d2s, s2d=s2d, chamfer=overall)
     if tnt_dir is not None:
         from surf_amd.evaluation import fscore
         t0 = time.perf_counter()
@@ -356,6 +398,9 @@ def run(args, state=None):
         if cloud is not None:
             res = fscore.evaluate_scene(points_path, tnt_dir, scene, mode="pcd", **kw)
             rec.update(pcd_precision=res["precision"], pcd_recall=res["recall"], pcd_fscore=res["fscore"])
+        if cloud_mesh_record is not None:
+            res = fscore.evaluate_scene(cloud_mesh_record["file"], tnt_dir, scene, mode="mesh", **kw)
+            cloud_mesh_record.update(precision=res["precision"], recall=res["recall"], fscore=res["fscore"])
         ms["evaluate_fscore"] = 1e3 * (time.perf_counter() - t0)
     with open(os.path.join(args.out_dir, f"fused_{name}.json"), "w") as f:
         json.dump(rec, f)

@@ -3230,3 +3230,99 @@ def points_stat_sums(stat):
     out = torch.empty(3, dtype=torch.float64, device=stat.device)
     _lib.lib().surf_points_stat_sums(_p(stat), stat.shape[0], _p(part), _p(out), _stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# point-set surface (point_surface.hip): a signed distance on the lattice bricks near an oriented cloud
+# ------------------------------------------------------------------------------------------------
+
+CLOUD_MAX_RING = 4                   # SURF_CLOUD_MAX_RING of include/surf_hip.h
+CLOUD_INDEX_BITS = 31                # a composite key is (brick key << 31) | caller index
+
+
+def cloud_ring(reach):
+    """ring = ceil(reach / 8) of rule 2 (include/surf_hip.h, above surf_cloud_brick_keys), as ValueError where the entry points
+    would return a status."""
+    reach = float(reach)
+    if not (reach > 0 and reach < 1e9):
+        raise ValueError(f"point surface: reach must be finite and > 0 lattice steps, got {reach}")
+    ring = int(np.ceil(reach / 8.0))
+    if ring > CLOUD_MAX_RING:
+        raise ValueError(f"point surface: the support reaches across {ring} bricks, at most {CLOUD_MAX_RING} are supported "
+                         f"(a radius just under {8 * CLOUD_MAX_RING} voxels)")
+    return ring
+
+
+def _cloud_frame(axes, lo, voxel):
+    nx, ny, nz = _chk_fuse_axes(axes)
+    lo = [float(v) for v in np.asarray(lo, np.float64).reshape(3)]
+    return (lo[0], lo[1], lo[2], float(voxel), nx, ny, nz)
+
+
+def cloud_sort(points, normals, colors, axes, lo, voxel, reach):
+    """Rules 1-3: (sorted_keys (m,) int64, sorted_points (m, 3), sorted_normals (m, 3), sorted_colors (m, 3) uint8 or None) of the
+    points of the cloud that take part, in ascending composite-key order.  points, normals (n, 3) fp32, colors (n, 3) uint8 or
+    None, device tensors.  One host read (m)."""
+    _chk(points, torch.float32, "points")
+    _chk(normals, torch.float32, "normals")
+    if points.dim() != 2 or points.shape[1] != 3 or normals.shape != points.shape:
+        raise ValueError(f"point surface: points and normals (n, 3), got {tuple(points.shape)} and {tuple(normals.shape)}")
+    if colors is not None:
+        _chk(colors, torch.uint8, "colors")
+        if colors.shape != points.shape:
+            raise ValueError(f"point surface: colors (n, 3) uint8, got {tuple(colors.shape)}")
+    n = int(points.shape[0])
+    if n > 2 ** 31 - 1:
+        raise ValueError(f"points: {n} points exceed int32 indexing")
+    ring = cloud_ring(reach)
+    frame = _cloud_frame(axes, lo, voxel)
+    keys = torch.empty(n, dtype=torch.int64, device=points.device)
+    _lib.lib().surf_cloud_brick_keys(_p(points), _p(normals), n, *frame, float(reach), _p(keys), _stream())
+    tail = 1
+    for a in frame[4:]:
+        tail *= (a + 7) // 8 + 2 * ring
+    skeys = torch.sort(keys)[0]
+    m = int((skeys < (tail << CLOUD_INDEX_BITS)).sum()) if n else 0
+    skeys = skeys[:m].contiguous()
+    order = skeys & ((1 << CLOUD_INDEX_BITS) - 1)
+    return (skeys, points[order].contiguous(), normals[order].contiguous(),
+            None if colors is None else colors[order].contiguous())
+
+
+def cloud_mark_bricks(mark, sorted_points, axes, lo, voxel, reach):
+    """Rule 6: mark (nbp^3 bytes, see fuse_brick_dims) gets a 1 at every brick a point of sorted_points (m, 3) allocates."""
+    _chk(mark, torch.uint8, "mark")
+    _chk(sorted_points, torch.float32, "sorted_points")
+    frame = _cloud_frame(axes, lo, voxel)
+    if mark.numel() != fuse_brick_dims(frame[4:])[1] ** 3:
+        raise ValueError("cloud_mark_bricks: mark holds one byte per brick of the table")
+    cloud_ring(reach)
+    _lib.lib().surf_cloud_mark_bricks(_p(sorted_points), int(sorted_points.shape[0]), *frame, float(reach), _p(mark), _stream())
+
+
+def cloud_field_bricks(sorted_cloud, bricks, axes, lo, voxel, reach, radius, min_points, staged=False):
+    """Rules 3-5 at every node of the listed bricks: (tsdf, weight (n_bricks * 512,), color (n_bricks * 512, 3) or None[, staged
+    (n_bricks,) int32: the candidates every brick ran through]).  sorted_cloud: cloud_sort's tuple."""
+    skeys, spts, snrm, scol = sorted_cloud
+    _chk(skeys, torch.int64, "sorted_keys")
+    _chk(spts, torch.float32, "sorted_points")
+    _chk(snrm, torch.float32, "sorted_normals")
+    _chk(bricks, torch.int32, "bricks")
+    m, nb = int(skeys.shape[0]), int(bricks.shape[0])
+    if spts.shape != (m, 3) or snrm.shape != (m, 3) or (scol is not None and (scol.dtype != torch.uint8 or scol.shape != (m, 3))):
+        raise ValueError("cloud_field_bricks: sorted keys (m,), points and normals (m, 3) fp32, colours (m, 3) uint8")
+    if int(min_points) != min_points or min_points < 1:
+        raise ValueError(f"cloud_field_bricks: min_points must be an integer >= 1, got {min_points}")
+    if nb * 512 >= 2 ** 31:
+        raise ValueError("point surface: 2^31 / 512 allocated bricks or more")
+    cloud_ring(reach)
+    frame = _cloud_frame(axes, lo, voxel)
+    dev = bricks.device
+    tsdf = torch.empty(nb * 512, dtype=torch.float32, device=dev)
+    weight = torch.empty(nb * 512, dtype=torch.float32, device=dev)
+    color = None if scol is None else torch.empty(nb * 512, 3, dtype=torch.float32, device=dev)
+    count = torch.empty(nb, dtype=torch.int32, device=dev) if staged else None
+    _lib.lib().surf_cloud_field_bricks(_p(skeys), _p(spts), _p(snrm), _p(scol), m, _p(bricks), nb, _p(axes[0]), _p(axes[1]),
+                                       _p(axes[2]), *frame[4:], *frame[:4], float(reach), ctypes.c_float(float(radius)),
+                                       int(min_points), _p(tsdf), _p(weight), _p(color), _p(count), _stream())
+    return (tsdf, weight, color) + ((count,) if staged else ())
