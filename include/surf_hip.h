@@ -1278,6 +1278,77 @@ int surf_cloud_field_bricks(const int64_t* sorted_keys, const float* sorted_poin
                             double lo_z, double voxel, double reach, float radius, int min_points, float* tsdf, float* weight,
                             float* color, int32_t* staged, void* stream);
 
+/*
+ * Mesh smoothing: Laplacian and Taubin lambda|mu steps with uniform (umbrella) weights on a triangle mesh
+ * (surf_amd/mesh_smooth.py, backend="device"; mesh_smooth.hip).  Added under SURF_ABI_VERSION 41 without a bump, like the entry
+ * points above.  The device path returns the host path's arrays: both follow the rule below, fp64 with separate multiplies and
+ * adds (-ffp-contract=off), positions rounded to fp32 after every step.  Faces, colours, vertex count and order never change.
+ *
+ * THE RULE.  vertices (n,3) fp32, all finite; faces (m,3) int32 with indices in [0, n); iterations >= 0; 0 < lam <= 1; mu absent
+ * or finite with mu < -lam; pin_boundary; max_move absent or finite and > 0; normals not wanted, wanted, or wanted and aligned
+ * with given normals (n,3) fp32.
+ *   1. edges.  A face (a,b,c) has the undirected edges {a,b}, {b,c}, {c,a}, in that order.  An edge with equal ends is dropped, and
+ *      so is an edge that an earlier edge of the SAME face equals, so that a face counts once at each of its edges.  i and j are
+ *      neighbours iff at least one face has the edge {i,j}; N(i) lists the neighbours of i once each in ascending index order and
+ *      d_i is its length (0 for a vertex without an edge: an ISOLATED vertex).  uses({i,j}) is the number of faces, a face listed
+ *      twice counted twice, that have the edge.  i is a BOUNDARY vertex iff uses({i,j}) == 1 for some j; edges of two, three or
+ *      more faces are interior.
+ *   2. one step with factor s (fp64).  x'_i = x_i to the bit if d_i == 0, or if pin_boundary and i is a boundary vertex.  Otherwise
+ *      per axis:  S = +0;  for j in N(i) ascending: S = S + (double)x_j;  m = S / (double)d_i;
+ *      x'_i = (float)((double)x_i + s * (m - (double)x_i)).  A step reads only the positions before it (Jacobi, two buffers).
+ *   3. schedule.  Without mu: `iterations` steps with s = lam (Laplacian).  With mu: `iterations` pairs, a step with s = lam and
+ *      then a step with s = mu (Taubin).
+ *   4. displacement cap, once after the last step, with M = max_move and x0 the input position:  d[a] = (double)x[a] -
+ *      (double)x0[a];  q = (d0*d0 + d1*d1) + d2*d2.  If q > M*M the vertex is CAPPED:  r = M / sqrt(q),
+ *      x[a] = (float)((double)x0[a] + d[a] * r).  The movement of a vertex is q of its final fp32 position (formed again after a
+ *      cap); moved_max = sqrt(max q), moved_rms = sqrt(Q / (double)n) with Q the sum of all q by the 256-ary sequential tree: the
+ *      values are cut into runs of 256 consecutive ones (the last may be shorter), every run is added from +0 in index order, and
+ *      the run sums are summed in the same way until one value is left.
+ *   5. normals, from the final positions.  Per face F = e1 x e2 in fp64 with e1 = p1 - p0, e2 = p2 - p0:
+ *      F = (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z, e1x*e2y - e1y*e2x).  Per vertex S[a] = the sum of F[a] over every corner of every
+ *      face that names it, in (face, corner) order from +0 (a face that names it twice is added twice);  L2 = (Sx*Sx + Sy*Sy) + Sz*Sz;
+ *      normal[a] = (float)(S[a] / sqrt(L2)), or (0,0,0) if L2 == 0 or L2 is not finite.  With given normals g:
+ *      t = ((double)nx*(double)gx + (double)ny*(double)gy) + (double)nz*(double)gz of the fp32 normal, and the normal is negated
+ *      iff t < 0: the orientation of whatever made g survives.
+ *
+ * Entry points, in the order surf_amd.ops.smooth_mesh calls them (sorts, scans and searches between them are the caller's).
+ * Positions travel between the steps as (n,4) fp32 rows of 16 bytes, (x, y, z, unused), so that a neighbour is one load.
+ *   surf_smooth_edge_keys: keys (6 m) int64.  Slot k of face f writes (lo << 32 | hi) to keys[6 f + 2 k] and (hi << 32 | lo) to
+ *     keys[6 f + 2 k + 1]: one directed key per end.  A dropped edge (rule 1) and every edge of a face with an index outside [0, n)
+ *     write SURF_SMOOTH_NO_KEY, which sorts behind every key; such a face also sets flag[0] = 1 (int32, zeroed by the caller),
+ *     which the CALLER reads before it goes on.
+ *   surf_smooth_adjacency: from sorted_keys (6 m) ascending and head_scan (6 m) int64, the INCLUSIVE scan of "differs from the key
+ *     before it" (head_scan[0] = 1): neighbours[head_scan[j] - 1] = low word of the first key of every run of equal keys (nnz =
+ *     the number of runs below SURF_SMOOTH_NO_KEY), which lists N(i) row after row; boundary (n) uint8, zeroed by the caller, gets
+ *     a 1 at the high word of every run of length one.  row_start (n + 1) int32, the first entry of every row, is the caller's
+ *     (a search of v << 32 in sorted_keys, looked up in head_scan).
+ *   surf_smooth_step: rule 2, positions_out = step(positions_in) with factor s; one vertex per lane.  A vertex of more than
+ *     SURF_SMOOTH_WAVE_DEGREE neighbours is summed by its whole wavefront, 64 gathers at a time, in the same order.
+ *   surf_smooth_cap: rule 4 from positions (n,4) and vertices0 (n,3): out_vertices (n,3) fp32, moved2 (n) fp64 = q of the final
+ *     position, capped (n) uint8.  max_move <= 0 means no cap.
+ *   surf_smooth_sum256: out (ceil(count / 256)) fp64 = the run sums of rule 4 of values (count) fp64; the caller repeats it until
+ *     one value is left.
+ *   surf_smooth_normals: rule 5.  corner_order (3 m) int64 = the stable ascending sort permutation of faces read as a flat array,
+ *     corner_start (n + 1) int64 the first position of every vertex in it; face_normals (m,3) fp64 is scratch; given_normals (n,3)
+ *     fp32 or null.
+ * n == 0 or m == 0 returns 0 at once where there is nothing to do.  n or m > SURF_SMOOTH_MAX_ITEMS is SURF_E_LIMIT (6 m directed
+ * edges are counted in int32).  A null pointer, nnz outside [0, 6 m], a factor or max_move that is not finite are SURF_E_ARG.
+ */
+#define SURF_SMOOTH_MAX_ITEMS 357913941         /* (2^31 - 1) / 6 */
+#define SURF_SMOOTH_NO_KEY 0x7fffffffffffffffLL
+#define SURF_SMOOTH_WAVE_DEGREE 32
+int surf_smooth_edge_keys(const int32_t* faces, int64_t m, int64_t n, int64_t* keys, int32_t* flag, void* stream);
+int surf_smooth_adjacency(const int64_t* sorted_keys, const int64_t* head_scan, int64_t m, int64_t n, int64_t nnz,
+                          int32_t* neighbours, uint8_t* boundary, void* stream);
+int surf_smooth_step(const float* positions_in, float* positions_out, int64_t n, const int32_t* row_start,
+                     const int32_t* neighbours, int64_t nnz, const uint8_t* boundary, int pin_boundary, double s, void* stream);
+int surf_smooth_cap(const float* positions, const float* vertices0, int64_t n, double max_move, float* out_vertices,
+                    double* moved2, uint8_t* capped, void* stream);
+int surf_smooth_sum256(const double* values, int64_t count, double* out, void* stream);
+int surf_smooth_normals(const float* vertices, int64_t n, const int32_t* faces, int64_t m, const int64_t* corner_order,
+                        const int64_t* corner_start, const float* given_normals, double* face_normals, float* normals,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

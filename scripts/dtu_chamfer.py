@@ -70,6 +70,17 @@ def parse_args(argv=None):
     ap.add_argument("--vertex_colors", action="store_true",
                     help="also write per-vertex normals (nx ny nz) and blended colours (red green blue) into the PLY "
                          "(ImplicitSurface.vertex_attributes on the final vertex set; geometry and Chamfer unchanged)")
+    ap.add_argument("--smooth_iters", type=int, default=None, metavar="N",
+                    help="smooth the mesh with N Taubin lambda|mu pairs (surf_amd/mesh_smooth.py) after --clean_mesh and before "
+                         "--simplify_cell; with --vertex_colors the normals are recomputed from the smoothed mesh, on the side of "
+                         "the ones they replace")
+    ap.add_argument("--smooth_lambda", type=float, default=0.5, help="0 < lambda <= 1: the shrinking step's factor")
+    ap.add_argument("--smooth_mu", type=float, default=-0.53, help="mu < -lambda: the inflating step's factor")
+    ap.add_argument("--smooth_laplacian", action="store_true", help="N plain Laplacian steps with --smooth_lambda, no mu step (shrinks)")
+    ap.add_argument("--smooth_max_move", type=float, default=None,
+                    help="no vertex ends further than this from where it started, in the mesh's own units (the normalised frame)")
+    ap.add_argument("--smooth_free_boundary", action="store_true", help="let the vertices on open edges move too (default: pinned)")
+    ap.add_argument("--smooth_backend", default="host", choices=["host", "device"])
     ap.add_argument("--simplify_cell", type=float, default=None,
                     help="simplify the mesh to one vertex per cell of this size, in the mesh's own units (the normalised frame the "
                          "val forward extracts it in), by quadric vertex clustering: the last mesh step, after --clean_mesh")
@@ -96,6 +107,7 @@ def run(args, state=None):
     from surf_amd.evaluation import clean_dtu
     from surf_amd.evaluation import clean_mesh as CM
     from surf_amd.mesh_simplify import simplify_step
+    from surf_amd.mesh_smooth import check_params, smooth_step
     from surf_amd.evaluation import dtu_eval
     from surf_amd.surf import SuRF
 
@@ -103,6 +115,14 @@ def run(args, state=None):
     protocol = args.clean_protocol if args.clean_mesh else None
     if protocol == "dtu_test" and args.dtu_test_dir is None:
         raise SystemExit("dtu_chamfer: --clean_protocol dtu_test needs --dtu_test_dir")
+    smooth = None
+    if getattr(args, "smooth_iters", None) is not None:      # a Namespace built by hand may lack the flags
+        try:
+            smooth = check_params({"iterations": args.smooth_iters, "lam": args.smooth_lambda,
+                                   "mu": None if args.smooth_laplacian else args.smooth_mu,
+                                   "pin_boundary": not args.smooth_free_boundary, "max_move": args.smooth_max_move})
+        except ValueError as e:
+            raise SystemExit(f"dtu_chamfer: {e}")
     cfg = C.parse_file(args.conf)
     dconf = cfg["val_dataset"]
     if args.data_dir is not None:
@@ -163,7 +183,7 @@ def run(args, state=None):
         os.makedirs(os.path.dirname(mesh_path), exist_ok=True)
         if state is not None:
             state.update(model=model, item=item, vertices=v, triangles=t)
-        attrs, t_attr, simplified = {}, None, None
+        attrs, t_attr, simplified, smoothed = {}, None, None, None
         if args.vertex_colors:                   # on the final vertex set: after clean_mesh, before scale_mat
             t0 = time.perf_counter()
             attrs = model.vertex_attributes(v)
@@ -178,6 +198,9 @@ def run(args, state=None):
             v = np.asarray(v)[kept]
             normals, colors = attrs.get("normals"), attrs.get("colors")
             normals, colors = (None if normals is None else normals[kept]), (None if colors is None else colors[kept])
+            if smooth is not None:               # in the normalised frame, like the simplification; the world-frame vertices follow
+                v, normals, smoothed = smooth_step(v, t, smooth, normals=normals, backend=args.smooth_backend, device=dev)
+                vw = mesh_io.transform_vertices(v, scale_mat)
             if args.simplify_cell is not None:   # the last mesh step, in the normalised frame; the world-frame vertices follow it
                 v, t, normals, colors, simplified = simplify_step(v, t, args.simplify_cell, normals, colors, args.simplify_backend, dev)
                 vw = mesh_io.transform_vertices(v, scale_mat)
@@ -188,6 +211,10 @@ def run(args, state=None):
             mesh_io.write_ply(mesh_path, vw, t, normals=normals, colors=colors)
         else:
             normals, colors = attrs.get("normals"), attrs.get("colors")
+            if smooth is not None:
+                v, normals, smoothed = smooth_step(v, t, smooth, normals=normals, backend=args.smooth_backend, device=dev)
+                if state is not None:
+                    state.update(vertices=v, triangles=t)
             if args.simplify_cell is not None:
                 v, t, normals, colors, simplified = simplify_step(v, t, args.simplify_cell, normals, colors, args.simplify_backend, dev)
                 if state is not None:
@@ -209,7 +236,7 @@ def run(args, state=None):
                 "clean_backend": args.clean_backend if args.clean_mesh else None, "clean_protocol": protocol,
                 "seconds": {"load": t_load, "val_forward": t_val, "clean": t_clean, "evaluate": t_eval,
                             **({} if t_attr is None else {"vertex_attributes": t_attr})},
-                **({} if simplified is None else {"simplify": simplified})}
+                **({} if smoothed is None else {"smooth": smoothed}), **({} if simplified is None else {"simplify": simplified})}
 
     if not args.sweep:
         rec = evaluate()

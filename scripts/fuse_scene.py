@@ -24,6 +24,10 @@ With --cloud_mesh [--cloud_mesh_radius VOXELS] [--cloud_mesh_min_points N] (need
 cloud is then meshed itself: a point-set surface on the same lattice (surf_amd/point_surface.py, csrc/point_surface.hip), simplified
 by --simplify_mm -> <N>_cloud_mesh.ply; the record gains `cloud_mesh` {radius, min_points, points, bricks, allocated_share, vertices,
 faces, file, ms} and, with --eval_dir / --tnt_dir, that mesh's scores inside it.
+With --smooth_iters N [--smooth_lambda L --smooth_mu M | --smooth_laplacian] [--smooth_max_move_mm X] [--smooth_free_boundary] the
+mesh is smoothed (surf_amd/mesh_smooth.py, csrc/mesh_smooth.hip: N Taubin lambda|mu pairs, or N Laplacian steps) after --clean_mesh
+and before --simplify_mm; positions move, faces and colours stay; the record gains `smooth` {iterations, lam, mu, pin_boundary,
+max_move, vertices, boundary_vertices, isolated_vertices, moved_max, moved_rms, capped, ms}.  --cloud_mesh is smoothed the same way.
 
 The lattice covers the union of the groups' normalised [-1, 1]^3 boxes (fusion.bounds_from_scale_mats; a first pass over the items
 reads their scale_mats) at --voxel_mm world units per step, or --resolution points along the longest side.
@@ -109,6 +113,16 @@ def parse_args(argv=None):
     ap.add_argument("--dtu_test_dir", default=None, help="DTU_TEST tree (cameras/, scan<N>/mask/) of --clean_mesh")
     ap.add_argument("--clean_set", type=int, default=1, choices=[0, 1], help="view set of --clean_mesh")
     ap.add_argument("--clean_backend", default="host", choices=["host", "device"])
+    ap.add_argument("--smooth_iters", type=int, default=None, metavar="N",
+                    help="smooth the mesh with N Taubin lambda|mu pairs (surf_amd/mesh_smooth.py): after --clean_mesh, before "
+                         "--simplify_mm; also applied to --cloud_mesh")
+    ap.add_argument("--smooth_lambda", type=float, default=0.5, help="0 < lambda <= 1: the shrinking step's factor")
+    ap.add_argument("--smooth_mu", type=float, default=-0.53, help="mu < -lambda: the inflating step's factor")
+    ap.add_argument("--smooth_laplacian", action="store_true", help="N plain Laplacian steps with --smooth_lambda, no mu step (shrinks)")
+    ap.add_argument("--smooth_max_move_mm", type=float, default=None,
+                    help="no vertex ends further than this from where it started (world units; DTU: millimetres)")
+    ap.add_argument("--smooth_free_boundary", action="store_true", help="let the vertices on open edges move too (default: pinned)")
+    ap.add_argument("--smooth_backend", default="host", choices=["host", "device"])
     ap.add_argument("--simplify_mm", type=float, default=None,
                     help="simplify the mesh to one vertex per cell of this size (world units; DTU: millimetres) by quadric vertex "
                          "clustering (surf_amd/mesh_simplify.py): the last mesh step, after --clean_mesh, before the PLY and the scores")
@@ -134,6 +148,21 @@ def parse_args(argv=None):
                     help="(tests) replace the U-Nets' matching logits by a sphere-concentrated field, as an untrained model needs")
     ap.add_argument("--device", default="cuda:0")
     return ap.parse_args(argv)
+
+
+def smooth_params(args):
+    """The --smooth_* flags as mesh_smooth's argument dict, or None without --smooth_iters (a Namespace built by hand may lack them)."""
+    iters = getattr(args, "smooth_iters", None)
+    if iters is None:
+        return None
+    from surf_amd.mesh_smooth import check_params
+    try:
+        return check_params({"iterations": iters, "lam": getattr(args, "smooth_lambda", 0.5),
+                             "mu": None if getattr(args, "smooth_laplacian", False) else getattr(args, "smooth_mu", -0.53),
+                             "pin_boundary": not getattr(args, "smooth_free_boundary", False),
+                             "max_move": getattr(args, "smooth_max_move_mm", None)})
+    except ValueError as e:
+        raise SystemExit(f"fuse_scene: {e}")
 
 
 def run(args, state=None):
@@ -169,6 +198,7 @@ def run(args, state=None):
     cloud_mesh_record = None
     if cloud_mesh and not (args.point_cloud and cloud_normals is not None):
         raise SystemExit("fuse_scene: --cloud_mesh needs --point_cloud and --cloud_normals (the surface is taken from oriented points)")
+    smooth = smooth_params(args)
     cfg = C.parse_file(args.conf)
     dconf = cfg["val_dataset"]
     if args.data_dir is not None:
@@ -264,7 +294,7 @@ def run(args, state=None):
                 radius = float(getattr(args, "cloud_mesh_radius", 3.0)) * voxel
                 min_points = int(getattr(args, "cloud_mesh_min_points", 4))
                 cm = point_surface.reconstruct(cloud, cloud_nrm, voxel, radius=radius, min_points=min_points, bounds=(lo, hi),
-                                               simplify_cell=args.simplify_mm, device=dev, stats=st)
+                                               simplify_cell=args.simplify_mm, device=dev, stats=st, smooth=smooth)
                 if len(cm[1]) == 0:
                     raise SystemExit("fuse_scene: --cloud_mesh found no zero crossing between observed lattice points (empty mesh)")
                 cloud_mesh_path = os.path.join(args.out_dir, "meshes", "fused", f"{name}_cloud_mesh.ply")
@@ -312,6 +342,10 @@ def run(args, state=None):
                                               device=dev.type, return_index=True)
         colors = None if colors is None else colors[kept]
         ms["clean"] = 1e3 * (time.perf_counter() - t0)
+    smoothed = None
+    if smooth is not None:                              # after the cleaner, whose masks are about the measured surface
+        from surf_amd.mesh_smooth import smooth_step
+        v, _, smoothed = smooth_step(v, t, smooth, backend=getattr(args, "smooth_backend", "host"), device=dev)
     simplified = None
     if args.simplify_mm is not None:                    # the last mesh step: the cleaner's component threshold is about the full mesh
         from surf_amd.mesh_simplify import simplify_step
@@ -357,6 +391,8 @@ def run(args, state=None):
            "colors": bool(args.colors), "cleaned": bool(args.clean_mesh), "mesh": mesh_path, "ms": ms}
     if args.sparse:                                     # without the flag the record is what it was
         rec.update(sparse=True, bricks=volume.n_bricks, allocated_share=volume.allocated_share(), state_bytes=volume.state_bytes())
+    if smoothed is not None:                            # without the flag the record is what it was
+        rec.update(smooth=smoothed)
     if simplified is not None:                          # without the flag the record is what it was
         rec.update(simplify=simplified)
     if model_residual is not None:                      # without the switch the record is what it was

@@ -1840,6 +1840,140 @@ def simplify_mesh(vertices, faces, cell, normals=None, colors=None, stages=None)
 
 
 # ------------------------------------------------------------------------------------------------
+# mesh smoothing (mesh_smooth.hip): Laplacian / Taubin steps with uniform weights; the rule is in include/surf_hip.h
+# ------------------------------------------------------------------------------------------------
+
+SMOOTH_HOST_READS = 2            # smooth_mesh waits for the device twice: see its docstring
+SMOOTH_MAX_ITEMS = (2 ** 31 - 1) // 6
+_SMOOTH_NO_KEY = 2 ** 63 - 1
+
+
+def smooth_adjacency(faces, n, also=()):
+    """Rule 1 of the surf_smooth_* group on a device tensor faces (m, 3) int32 of a mesh with n vertices, m, n >= 1:
+    (row_start (n + 1) int32, neighbours (nnz) int32, boundary (n) uint8, values of `also`).  neighbours[row_start[i] :
+    row_start[i + 1]] is N(i) ascending.  One read of the device: [nnz, smallest and largest face index] and the 0-dim tensors of
+    `also`, whose values come back as Python numbers; a face index outside [0, n) raises ValueError after it."""
+    _chk(faces, torch.int32, "faces")
+    m, dev = faces.shape[0], faces.device
+    if max(n, m) > SMOOTH_MAX_ITEMS:
+        _lib.check(-2, f"smooth_mesh: {n} vertices / {m} faces")
+    L, s = _lib.lib(), _stream()
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    keys = torch.empty(6 * m, dtype=torch.int64, device=dev)
+    L.surf_smooth_edge_keys(_p(faces), m, n, _p(keys), _p(flag), s)
+    skeys = torch.sort(keys)[0]
+    del keys
+    head = torch.ones(6 * m, dtype=torch.bool, device=dev)
+    head[1:] = skeys[1:] != skeys[:-1]
+    hscan = torch.cumsum(head, 0, dtype=torch.int64)
+    # the first entry of every row: the runs in front of the first key >= (v << 32); every key below NO_KEY is below (n << 32)
+    pos = torch.searchsorted(skeys, torch.arange(n + 1, dtype=torch.int64, device=dev) << 32)
+    starts = torch.where(pos > 0, hscan[(pos - 1).clamp_(min=0)], torch.zeros_like(pos))
+    f_lo, f_hi = torch.aminmax(faces)
+    read = torch.stack([starts[n].double(), f_lo.double(), f_hi.double()] + [t.double() for t in also]).tolist()      # host read
+    nnz, lo, hi = (int(x) for x in read[:3])
+    if lo < 0 or hi >= n:
+        raise ValueError(f"face indices span [{lo}, {hi}], the mesh has {n} vertices")
+    neighbours = torch.empty(nnz, dtype=torch.int32, device=dev)
+    boundary = torch.zeros(n, dtype=torch.uint8, device=dev)
+    L.surf_smooth_adjacency(_p(skeys), _p(hscan), m, n, nnz, _p(neighbours), _p(boundary), s)
+    return starts.to(torch.int32), neighbours, boundary, read[3:]
+
+
+def smooth_normals(vertices, faces, given=None):
+    """Rule 5 of the surf_smooth_* group on device tensors: (n, 3) fp32 vertex normals of vertices (n, 3) fp32 and faces (m, 3)
+    int32, kept on the side of `given` (n, 3) fp32 when that is not None.  No read of the device; the face indices must be valid."""
+    _chk(vertices, torch.float32, "vertices")
+    _chk(faces, torch.int32, "faces")
+    n, m, dev = vertices.shape[0], faces.shape[0], vertices.device
+    if max(n, m) > SMOOTH_MAX_ITEMS:
+        _lib.check(-2, f"smooth_normals: {n} vertices / {m} faces")
+    if given is not None:
+        _chk(given, torch.float32, "normals")
+        if tuple(given.shape) != (n, 3):
+            raise ValueError(f"smooth_mesh: normals {tuple(given.shape)} for {n} vertices")
+    out = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    sorted_v, corder = torch.sort(faces.reshape(-1), stable=True)      # stable: a vertex lists its corners in (face, corner) order
+    cstart = torch.searchsorted(sorted_v, torch.arange(n + 1, dtype=torch.int32, device=dev))
+    scratch = torch.empty(m, 3, dtype=torch.float64, device=dev)
+    _lib.lib().surf_smooth_normals(_p(vertices), n, _p(faces), m, _p(corder), _p(cstart), _p(given), _p(scratch), _p(out), _stream())
+    return out
+
+
+def smooth_mesh(vertices, faces, iterations=10, lam=0.5, mu=-0.53, pin_boundary=True, max_move=None, normals=None, stages=None):
+    """The surf_smooth_* rule on device tensors: vertices (n, 3) fp32, faces (m, 3) int32, normals None, True or (n, 3) fp32 ->
+    (vertices (n, 3) fp32, normals (n, 3) fp32 or None, info); the arguments and info are surf_amd.mesh_smooth.smooth_mesh's.
+    The sorts, scans and searches between the kernels are torch's.  Exactly SMOOTH_HOST_READS reads of the device, each one small
+    copy: (1) [number of neighbour entries, smallest and largest face index, all vertices finite] before any step, (2) [boundary
+    vertices, isolated vertices, largest and summed squared movement, capped vertices] for info; an empty mesh reads nothing.  A
+    face index outside the vertex list or a vertex that is not finite raises ValueError after (1), before any step.
+    stages: a list that receives (name, start event, end event) per stage (scripts/time_mesh_smooth.py)."""
+    from .mesh_smooth import check_args, schedule
+    _chk(vertices, torch.float32, "vertices")
+    _chk(faces, torch.int32, "faces")
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"smooth_mesh: expected (n, 3) vertices and (m, 3) faces, got {tuple(vertices.shape)}, {tuple(faces.shape)}")
+    iterations, lam, mu, pin_boundary, max_move = check_args(iterations, lam, mu, pin_boundary, max_move)
+    n, m, dev = vertices.shape[0], faces.shape[0], vertices.device
+    if max(n, m) > SMOOTH_MAX_ITEMS:
+        _lib.check(-2, f"smooth_mesh: {n} vertices / {m} faces")
+    given = None if normals is None or normals is True else normals
+    if given is not None:
+        _chk(given, torch.float32, "normals")
+        if tuple(given.shape) != (n, 3):
+            raise ValueError(f"smooth_mesh: normals {tuple(given.shape)} for {n} vertices")
+    if n == 0 or m == 0:
+        nrm = given if given is not None else (torch.zeros(n, 3, dtype=torch.float32, device=dev) if normals is True else None)
+        return vertices, nrm, {"vertices": n, "boundary_vertices": 0, "isolated_vertices": n, "moved_max": 0.0, "moved_rms": 0.0,
+                               "capped": 0}
+
+    def stage(name):
+        if stages is not None:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            if stages:
+                stages[-1] = stages[-1][:2] + (ev,)
+            if name is not None:
+                stages.append((name, ev, None))
+
+    L, s = _lib.lib(), _stream()
+    stage("adjacency")
+    row_start, neighbours, boundary, (finite,) = smooth_adjacency(faces, n, also=(torch.isfinite(vertices).all(),))   # host read 1
+    if not finite:
+        i = int(torch.nonzero(~torch.isfinite(vertices).all(dim=1))[0, 0])
+        raise ValueError(f"smooth_mesh: vertex {i} is not finite: {vertices[i].tolist()}")
+    nnz = neighbours.shape[0]
+    stage("steps")
+    a = torch.zeros(n, 4, dtype=torch.float32, device=dev)             # 16-byte rows: a neighbour is one load
+    a[:, :3] = vertices
+    b = torch.empty_like(a)
+    for factor in schedule(iterations, lam, mu):
+        L.surf_smooth_step(_p(a), _p(b), n, _p(row_start), _p(neighbours), nnz, _p(boundary), int(pin_boundary), factor, s)
+        a, b = b, a
+    stage("cap")
+    out = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    moved2 = torch.empty(n, dtype=torch.float64, device=dev)
+    capped = torch.empty(n, dtype=torch.uint8, device=dev)
+    L.surf_smooth_cap(_p(a), _p(vertices), n, 0.0 if max_move is None else max_move, _p(out), _p(moved2), _p(capped), s)
+    total = moved2
+    while total.shape[0] > 1:                                          # rule 4's 256-ary sequential tree
+        runs = torch.empty((total.shape[0] + 255) // 256, dtype=torch.float64, device=dev)
+        L.surf_smooth_sum256(_p(total), total.shape[0], _p(runs), s)
+        total = runs
+    nrm = None
+    if normals is not None:
+        stage("normals")
+        nrm = smooth_normals(out, faces, given)
+    stage(None)
+    isolated = (row_start[1:] == row_start[:-1]).sum()
+    nb, ni, qmax, qsum, nc = torch.stack([boundary.sum().double(), isolated.double(), moved2.max(), total[0],
+                                          capped.sum().double()]).tolist()                                   # host read 2
+    info = {"vertices": n, "boundary_vertices": int(nb), "isolated_vertices": int(ni), "moved_max": float(np.sqrt(qmax)),
+            "moved_rms": float(np.sqrt(qsum / float(n))), "capped": int(nc)}
+    return out, nrm, info
+
+
+# ------------------------------------------------------------------------------------------------
 # the DTU protocol's mesh cleaner (dtu_clean.hip): elliptical dilation, rounded projection into padded masks, vertex removal
 # ------------------------------------------------------------------------------------------------
 
