@@ -105,8 +105,11 @@ int surf_sdf_mlp(const float* pts, const uint8_t* mask, const int32_t* idx, int6
  *           (dropped terms <= 2^-23 per product): fp32-equivalent results.  The packed image is opaque: the kernel works in
  *           units of the softplus exponent (biases and input columns x 100 log2 e, lin6's row 0 x ln 2 / 100, hidden matrices
  *           as they are), so an image is only meaningful to the kernel of the same library build.
- *   f16x2:  two fp16 pieces per operand (22 significant bits, second piece scaled by 2^11), three partial products:
- *           operand error <= 2^-22; activations must stay below 65504 in magnitude.  The fast path.
+ *   f16x2:  two fp16 pieces per operand, three partial products (the product of the two second pieces is dropped).  The
+ *           second piece is the fp16 of the fp32 residual v - fp16(v), at the operand's own scale: weights (and the reverse
+ *           sweep's deltas) are stored x 2^8 as a whole, activations unscaled.  Operand error <= 2^-22 relative while the
+ *           second piece is a normal fp16 number, <= 2^-25 absolute (2^-33 for the x 2^8 operands) below that; activations
+ *           must stay below 65504 in magnitude, weights below 65504 / 2^8.  The fast path.
  */
 int64_t surf_sdf_bf16_packed_bytes(void);
 int64_t surf_sdf_bf16_scratch_bytes(int64_t n_points);
