@@ -1352,6 +1352,91 @@ int surf_smooth_normals(const float* vertices, int64_t n, const int32_t* faces, 
                         const int64_t* corner_start, const float* given_normals, double* face_normals, float* normals,
                         void* stream);
 
+/*
+ * Mesh deviation: the exact distance from a point to a triangle mesh, and from it the two-sided vertex-sampled deviation between
+ * two meshes (surf_amd/mesh_distance.py, backend="device"; mesh_distance.hip).  Added under SURF_ABI_VERSION 41 without a bump,
+ * like the entry points above.  The device path returns the host path's arrays: both follow the rule below.
+ *
+ * THE RULE.  vertices (n,3) fp32, all finite; faces (m,3) int32 with indices in [0, n); points (k,3) fp32, all finite; max_dist
+ * finite and > 0.  All arithmetic is fp64 on the exactly converted fp32 values, multiplies and adds separate (-ffp-contract=off);
+ * dot(u,v) = (u0*v0 + u1*v1) + u2*v2; vector expressions are taken per axis.
+ *   PAIR VALUE q(p, face) with a, b, c the face's corners in order (the region scheme of Ericson, Real-Time Collision Detection,
+ *   5.1.5):
+ *     ab=b-a  ac=c-a  ap=p-a   d1=dot(ab,ap) d2=dot(ac,ap)
+ *     bp=p-b                   d3=dot(ab,bp) d4=dot(ac,bp)
+ *     cp=p-c                   d5=dot(ab,cp) d6=dot(ac,cp)
+ *     vc=d1*d4-d3*d2   vb=d5*d2-d1*d6   va=d3*d6-d5*d4   e1=d4-d3   e2=d5-d6
+ *     the first test that holds, in this order, names the REGION:
+ *      0: d1<=0 && d2<=0                        c* = a
+ *      1: d3>=0 && d4<=d3                       c* = b
+ *      2: vc<=0 && d1>=0 && d3<=0 && d1>d3      c* = a + ab*(d1/(d1-d3))
+ *      3: d6>=0 && d5<=d6                       c* = c
+ *      4: vb<=0 && d2>=0 && d6<=0               c* = a + ac*(d2/(d2-d6))
+ *      5: va<=0 && e1>=0 && e2>=0               c* = b + (c-b)*(e1/(e1+e2))
+ *      6: otherwise   den=1/((va+vb)+vc)        c* = (a + ab*(vb*den)) + ac*(vc*den)
+ *     e = p - c*;  q = dot(e,e)
+ *   Only the quotient of the region taken is part of the value.  Degenerate faces take part through the same tests.  d1 > d3 in
+ *   test 2 is there for them: d1 - d3 is |ab|^2, and without it a face with a == b would answer 0/0 for every point that is not
+ *   nearest to a; with it such a face is the segment a-c (tests 3 and 4).  a == c, b == c, a == b == c and collinear corners never
+ *   reach a vanishing divisor.  A pair whose q is NaN is ignored.
+ *   PER QUERY.  Q = the least non-NaN q over ALL faces; face = the smallest face index that attains it; closest = that pair's c*
+ *   (fp64); distance = sqrt(Q).  If distance < max_dist does not hold (no face at all, for one): distance +inf, face -1, closest
+ *   (+inf, +inf, +inf).  The value is a minimum over all faces: it does not depend on how the faces are searched.
+ *   DEVIATION of mesh A against mesh B.  "forward" queries the vertices of A that at least one face of A names, in index order,
+ *   against B; "backward" is the same with A and B exchanged.  Per direction: count (queries), beyond (queries answered +inf), and
+ *   over the rest max, mean = S1 / found and rms = sqrt(S2 / found), where S1 and S2 are the sums of distance and of
+ *   distance * distance in query order by the 256-ary sequential tree of the smoothing rule 4 (surf_smooth_sum256; a `beyond`
+ *   query contributes +0).  Nothing found: max, mean and rms are absent.  hausdorff = the larger of the two max, absent if either
+ *   is.  The default max_dist is the diagonal of the joint bounding box of all vertices of both meshes.
+ *
+ * THE SEARCH is a dense cell table over the bounding box of the vertices the faces name, nx * ny * nz cells of size `cell` from
+ * (lo_x, lo_y, lo_z); a coordinate x lies in cell floor((x - lo) / cell) of its axis, clamped to the table.  Every face is
+ * listed in every cell that its axis-aligned box overlaps: a (cell, face) PAIR.  A query walks shells of cells around its own
+ * cell, as surf_fscore_nearest does: after shells 0 .. k-1 every unlisted face lies more than R = (k - 1) * cell * (1 - 1e-6)
+ * away (its nearest point is inside its box, hence in an unvisited cell), and the walk stops once Q < R * R STRICTLY (a face at
+ * exactly R could still tie with a smaller index) or R >= max_dist.  A query outside the table starts at the first shell that
+ * touches it and answers +inf at once if that shell is beyond ceil(max_dist / (cell * (1 - 1e-6))) + 1.
+ *   Why the margin also covers the rounding of q: the dots of a pair are sums of products of differences of size at most
+ *   L + d (L the face's extent, d the distance), so the computed q is off by a few 2^-53 (L + d)^2, while R * R stands 2e-6 R * R
+ *   below the true bound.  For d near R >= cell that needs 2^-53 (L / cell + 1)^2 << 2e-6, i.e. L / cell far below 1e5.  The
+ *   caller keeps no more than SURF_MESHDIST_MAX_AXIS_CELLS cells along an axis, so L / cell < 1.8 * 4096.
+ *   PAIR BUDGET (surf_amd.ops.point_to_mesh): the cell starts at about four cells per face by volume and grows by 1.25 until the
+ *   pairs number at most max(SURF_MESHDIST_PAIRS_PER_FACE * m, 2^16).  A pair costs a 48-byte record and a sort entry, and every
+ *   further listing of a face is one more evaluation by the queries that pass it, so the budget bounds the table at 8 x 60 bytes
+ *   per face and the repeats at a small factor; 2^16 lets a small mesh keep fine cells.  A tuning choice, not measured against
+ *   others (the meshes measured came to 2.4 to 4.0 pairs per face without a growth).
+ *
+ * Entry points, in the order surf_amd.ops.point_to_mesh calls them (scans, sorts and gathers between them are the caller's).
+ *   surf_meshdist_pairs_count: records (m,12) fp32 = (a, b, c, the face index as int32 bits, 0, 0): 48 bytes, three 16-byte
+ *     loads; counts (m) int64 = the cells the face's box overlaps.  A face with an index outside [0, n) gets a zero record and
+ *     count 0 (the caller has refused such faces before).
+ *   surf_meshdist_pairs_emit: from records and starts (m) int64, the EXCLUSIVE scan of counts with `pairs` their total:
+ *     pair_cell[starts[f] + i] int64 = (x * ny + y) * nz + z of the i-th cell of face f, pair_face[...] int32 = f.  No order is
+ *     promised within a cell, and none is needed.  One lane per face: a face that spans the table is written by one lane.
+ *   surf_meshdist_query: the hot kernel, one lane per query.  cell_records (pairs,12) fp32 = the records in cell order, cell_start
+ *     (nx ny nz + 1) int32 the first record of every cell.  order (k) int64 = a permutation of the queries (the caller sorts them
+ *     by cell, so that the 64 lanes of a wavefront walk the same cells and read the same records); lane t serves query order[t]
+ *     and writes ITS rows: distance (k) fp64, face (k) int64, closest (k,3) fp64.  No sqrt and no division outside the region
+ *     taken inside the walk; every loop is bounded by the shell limit and the clipped table range.
+ * k == 0 or m == 0 returns 0 at once.  Null pointers, a cell or max_dist that is not finite and > 0, a lo that is not finite, a
+ * table dimension < 1 and pairs < 0 are SURF_E_ARG; n, m, k or pairs > 2^31 - 1, a dimension > SURF_MESHDIST_MAX_AXIS_CELLS and
+ * nx ny nz > SURF_MESHDIST_MAX_CELLS are SURF_E_LIMIT; all reported before any launch.
+ * Measured on an MI355X (scripts/time_mesh_distance.py, profiles/mesh_distance.txt), a 589 k-face mesh against its 10-pair Taubin
+ * smoothing, 299 k queries a direction: pairs 1.9 ms, sort 0.9 ms, query 1.3 ms; 2.4 pairs per face, 240 pairs evaluated per query.
+ */
+#define SURF_MESHDIST_MAX_AXIS_CELLS 4096
+#define SURF_MESHDIST_MAX_CELLS 67108864        /* 2^26 */
+#define SURF_MESHDIST_PAIRS_PER_FACE 8
+int surf_meshdist_pairs_count(const float* vertices, int64_t n, const int32_t* faces, int64_t m, double lo_x, double lo_y,
+                              double lo_z, double cell, int64_t nx, int64_t ny, int64_t nz, float* records, int64_t* counts,
+                              void* stream);
+int surf_meshdist_pairs_emit(const float* records, int64_t m, double lo_x, double lo_y, double lo_z, double cell, int64_t nx,
+                             int64_t ny, int64_t nz, const int64_t* starts, int64_t pairs, int64_t* pair_cell, int32_t* pair_face,
+                             void* stream);
+int surf_meshdist_query(const float* points, const int64_t* order, int64_t k, const float* cell_records, int64_t pairs,
+                        const int32_t* cell_start, double lo_x, double lo_y, double lo_z, double cell, int64_t nx, int64_t ny,
+                        int64_t nz, double max_dist, double* distance, int64_t* face, double* closest, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

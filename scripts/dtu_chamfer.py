@@ -85,6 +85,13 @@ def parse_args(argv=None):
                     help="simplify the mesh to one vertex per cell of this size, in the mesh's own units (the normalised frame the "
                          "val forward extracts it in), by quadric vertex clustering: the last mesh step, after --clean_mesh")
     ap.add_argument("--simplify_backend", default="host", choices=["host", "device"])
+    ap.add_argument("--deviation", action="store_true",
+                    help="report how far --smooth_iters / --simplify_cell moved the surface: the vertex-sampled deviation between "
+                         "the mesh before them and the mesh that is written, in the mesh's own units (surf_amd/mesh_distance.py)")
+    ap.add_argument("--deviation_backend", default="host", choices=["host", "device"])
+    ap.add_argument("--deviation_max_dist", type=float, default=None,
+                    help="vertices without a face of the other mesh nearer than this count as `beyond` (default: the diagonal of "
+                         "the two meshes' joint bounding box)")
     ap.add_argument("--downsample_density", type=float, default=0.2)
     ap.add_argument("--patch_size", type=float, default=60)
     ap.add_argument("--max_dist", type=float, default=20)
@@ -123,6 +130,9 @@ def run(args, state=None):
                                    "pin_boundary": not args.smooth_free_boundary, "max_move": args.smooth_max_move})
         except ValueError as e:
             raise SystemExit(f"dtu_chamfer: {e}")
+    deviation = bool(getattr(args, "deviation", False))
+    if deviation and smooth is None and args.simplify_cell is None:
+        raise SystemExit("dtu_chamfer: --deviation compares the mesh before and after --smooth_iters / --simplify_cell: give one of them")
     cfg = C.parse_file(args.conf)
     dconf = cfg["val_dataset"]
     if args.data_dir is not None:
@@ -198,6 +208,7 @@ def run(args, state=None):
             v = np.asarray(v)[kept]
             normals, colors = attrs.get("normals"), attrs.get("colors")
             normals, colors = (None if normals is None else normals[kept]), (None if colors is None else colors[kept])
+            before = (v, t)                      # mesh A of --deviation: after the cleaner, before the steps it measures
             if smooth is not None:               # in the normalised frame, like the simplification; the world-frame vertices follow
                 v, normals, smoothed = smooth_step(v, t, smooth, normals=normals, backend=args.smooth_backend, device=dev)
                 vw = mesh_io.transform_vertices(v, scale_mat)
@@ -211,6 +222,7 @@ def run(args, state=None):
             mesh_io.write_ply(mesh_path, vw, t, normals=normals, colors=colors)
         else:
             normals, colors = attrs.get("normals"), attrs.get("colors")
+            before = (v, t)
             if smooth is not None:
                 v, normals, smoothed = smooth_step(v, t, smooth, normals=normals, backend=args.smooth_backend, device=dev)
                 if state is not None:
@@ -222,6 +234,14 @@ def run(args, state=None):
             mesh_io.export_mesh(mesh_path, v, t, item["scale_mat"], normals=normals, colors=colors)   # runner.py:236-240
         if len(t) == 0:
             raise SystemExit(f"dtu_chamfer: --simplify_cell {args.simplify_cell} leaves no face (the cell swallows the mesh)")
+        deviated = None
+        if deviation:                            # mesh B is the mesh that is written, both in the normalised frame
+            from surf_amd.mesh_distance import deviation_step
+            try:
+                deviated = deviation_step(before[0], before[1], v, t, getattr(args, "deviation_max_dist", None),
+                                          backend=getattr(args, "deviation_backend", "host"), device=dev)
+            except ValueError as e:
+                raise SystemExit(f"dtu_chamfer: {e}")
         t0 = time.perf_counter()
         d2s, s2d, overall = dtu_eval.evaluate_scan(mesh_path, args.eval_dir, args.scan, patch_size=args.patch_size,
                                                    max_dist=args.max_dist, downsample_density=args.downsample_density,
@@ -236,7 +256,8 @@ def run(args, state=None):
                 "clean_backend": args.clean_backend if args.clean_mesh else None, "clean_protocol": protocol,
                 "seconds": {"load": t_load, "val_forward": t_val, "clean": t_clean, "evaluate": t_eval,
                             **({} if t_attr is None else {"vertex_attributes": t_attr})},
-                **({} if smoothed is None else {"smooth": smoothed}), **({} if simplified is None else {"simplify": simplified})}
+                **({} if smoothed is None else {"smooth": smoothed}), **({} if simplified is None else {"simplify": simplified}),
+                **({} if deviated is None else {"deviation": deviated})}
 
     if not args.sweep:
         rec = evaluate()

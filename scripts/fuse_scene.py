@@ -28,6 +28,10 @@ With --smooth_iters N [--smooth_lambda L --smooth_mu M | --smooth_laplacian] [--
 mesh is smoothed (surf_amd/mesh_smooth.py, csrc/mesh_smooth.hip: N Taubin lambda|mu pairs, or N Laplacian steps) after --clean_mesh
 and before --simplify_mm; positions move, faces and colours stay; the record gains `smooth` {iterations, lam, mu, pin_boundary,
 max_move, vertices, boundary_vertices, isolated_vertices, moved_max, moved_rms, capped, ms}.  --cloud_mesh is smoothed the same way.
+With --deviation [--deviation_backend device] [--deviation_max_mm X] (needs --smooth_iters or --simplify_mm) the record gains
+`deviation` {forward, backward, hausdorff, max_dist, ms}: the vertex-sampled deviation (surf_amd/mesh_distance.py, exact
+point-to-triangle distances) between the mesh after --clean_mesh and the mesh that is written; with --cloud_mesh the `cloud_mesh`
+block gains the same `deviation` for the cloud mesh (its surface is extracted a second time without the mesh steps).
 
 The lattice covers the union of the groups' normalised [-1, 1]^3 boxes (fusion.bounds_from_scale_mats; a first pass over the items
 reads their scale_mats) at --voxel_mm world units per step, or --resolution points along the longest side.
@@ -127,6 +131,13 @@ def parse_args(argv=None):
                     help="simplify the mesh to one vertex per cell of this size (world units; DTU: millimetres) by quadric vertex "
                          "clustering (surf_amd/mesh_simplify.py): the last mesh step, after --clean_mesh, before the PLY and the scores")
     ap.add_argument("--simplify_backend", default="host", choices=["host", "device"])
+    ap.add_argument("--deviation", action="store_true",
+                    help="report how far --smooth_iters / --simplify_mm moved the surface: the vertex-sampled deviation between the "
+                         "mesh before them and the mesh that is written (surf_amd/mesh_distance.py)")
+    ap.add_argument("--deviation_backend", default="host", choices=["host", "device"])
+    ap.add_argument("--deviation_max_mm", type=float, default=None,
+                    help="vertices without a face of the other mesh nearer than this count as `beyond` (world units; default: "
+                         "the diagonal of the two meshes' joint bounding box)")
     ap.add_argument("--eval_dir", default=None, help="DTU evaluation data (ObsMask/, Points/stl/): also report the Chamfer distance")
     ap.add_argument("--eval_device", default="cpu", choices=["cpu", "gpu"])
     ap.add_argument("--downsample_density", type=float, default=0.2)
@@ -199,6 +210,9 @@ def run(args, state=None):
     if cloud_mesh and not (args.point_cloud and cloud_normals is not None):
         raise SystemExit("fuse_scene: --cloud_mesh needs --point_cloud and --cloud_normals (the surface is taken from oriented points)")
     smooth = smooth_params(args)
+    deviation = bool(getattr(args, "deviation", False))
+    if deviation and smooth is None and args.simplify_mm is None:
+        raise SystemExit("fuse_scene: --deviation compares the mesh before and after --smooth_iters / --simplify_mm: give one of them")
     cfg = C.parse_file(args.conf)
     dconf = cfg["val_dataset"]
     if args.data_dir is not None:
@@ -297,11 +311,23 @@ def run(args, state=None):
                                                simplify_cell=args.simplify_mm, device=dev, stats=st, smooth=smooth)
                 if len(cm[1]) == 0:
                     raise SystemExit("fuse_scene: --cloud_mesh found no zero crossing between observed lattice points (empty mesh)")
+                cloud_deviated = None
+                if deviation:                           # mesh A: the same surface extracted again without the mesh steps
+                    from surf_amd.mesh_distance import deviation_step
+                    ca = point_surface.reconstruct(cloud, cloud_nrm, voxel, radius=radius, min_points=min_points, bounds=(lo, hi),
+                                                   device=dev)
+                    try:
+                        cloud_deviated = deviation_step(ca[0], ca[1], cm[0], cm[1], getattr(args, "deviation_max_mm", None),
+                                                        backend=getattr(args, "deviation_backend", "host"), device=dev)
+                    except ValueError as e:
+                        raise SystemExit(f"fuse_scene: {e}")
                 cloud_mesh_path = os.path.join(args.out_dir, "meshes", "fused", f"{name}_cloud_mesh.ply")
                 mesh_io.write_ply(cloud_mesh_path, cm[0], cm[1], colors=cm[2] if len(cm) > 2 else None)
                 cloud_mesh_record = {"radius": radius, "min_points": min_points, "points": st["points"], "bricks": st["bricks"],
                                      "allocated_share": st["allocated_share"], "vertices": st["vertices"], "faces": st["faces"],
                                      "file": cloud_mesh_path, "ms": 1e3 * (time.perf_counter() - t0)}
+                if cloud_deviated is not None:          # without the flag the block is what it was
+                    cloud_mesh_record["deviation"] = cloud_deviated
         else:
             mesh_io.write_ply_points(points_path, cloud.points, cloud.colors)
         cloud_views.clear()
@@ -342,6 +368,7 @@ def run(args, state=None):
                                               device=dev.type, return_index=True)
         colors = None if colors is None else colors[kept]
         ms["clean"] = 1e3 * (time.perf_counter() - t0)
+    before = (v, t) if deviation else None              # mesh A of --deviation: after the cleaner, before the steps it measures
     smoothed = None
     if smooth is not None:                              # after the cleaner, whose masks are about the measured surface
         from surf_amd.mesh_smooth import smooth_step
@@ -352,6 +379,14 @@ def run(args, state=None):
         v, t, _, colors, simplified = simplify_step(v, t, args.simplify_mm, colors=colors, backend=args.simplify_backend, device=dev)
         if len(t) == 0:
             raise SystemExit(f"fuse_scene: --simplify_mm {args.simplify_mm} leaves no face (the cell swallows the mesh)")
+    deviated = None
+    if before is not None:                              # mesh B is the mesh that is written
+        from surf_amd.mesh_distance import deviation_step
+        try:
+            deviated = deviation_step(before[0], before[1], v, t, getattr(args, "deviation_max_mm", None),
+                                      backend=getattr(args, "deviation_backend", "host"), device=dev)
+        except ValueError as e:
+            raise SystemExit(f"fuse_scene: {e}")
     t0 = time.perf_counter()
     mesh_path = os.path.join(args.out_dir, "meshes", "fused", f"{name}.ply")
     mesh_io.write_ply(mesh_path, v, t, colors=colors)
@@ -362,6 +397,8 @@ def run(args, state=None):
             state.update(cloud=cloud)
         if cloud_mesh_record is not None:
             state.update(cloud_mesh=cm)
+            if cloud_mesh_record.get("deviation") is not None:
+                state.update(cloud_mesh_before=ca)
     model_residual = None
     if render_dir is not None:
         # ---- the fused model seen from every fused view's camera: no mesh involved, one kernel launch and one copy per view ----
@@ -395,6 +432,8 @@ def run(args, state=None):
         rec.update(smooth=smoothed)
     if simplified is not None:                          # without the flag the record is what it was
         rec.update(simplify=simplified)
+    if deviated is not None:                            # without the flag the record is what it was
+        rec.update(deviation=deviated)
     if model_residual is not None:                      # without the switch the record is what it was
         rec.update(model_residual=model_residual, render_views_ms=render_ms)
     if filtered is not None:

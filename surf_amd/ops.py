@@ -1974,6 +1974,147 @@ def smooth_mesh(vertices, faces, iterations=10, lam=0.5, mu=-0.53, pin_boundary=
 
 
 # ------------------------------------------------------------------------------------------------
+# mesh deviation (mesh_distance.hip): exact point-to-triangle distances; the rule is in include/surf_hip.h
+# ------------------------------------------------------------------------------------------------
+
+MESHDIST_HOST_READS = 2          # the LEAST point_to_mesh waits for the device: one more per growth of the cell, see its docstring
+MESHDIST_MAX_AXIS_CELLS = 4096   # SURF_MESHDIST_MAX_AXIS_CELLS of include/surf_hip.h
+MESHDIST_MAX_CELLS = 1 << 26     # SURF_MESHDIST_MAX_CELLS
+MESHDIST_PAIRS_PER_FACE = 8      # SURF_MESHDIST_PAIRS_PER_FACE
+MESHDIST_MIN_PAIR_BUDGET = 1 << 16
+
+
+def meshdist_cell_dims(ext, m, start_cell=None):
+    """(cell, dims) of the cell table over a box of extents `ext` that holds m faces: _table_cell_dims with at most
+    MESHDIST_MAX_AXIS_CELLS - 1 cells along an axis and MESHDIST_MAX_CELLS in all.  Pure host arithmetic, shared with the host path."""
+    return _table_cell_dims(ext, m, max(ext) / (MESHDIST_MAX_AXIS_CELLS - 2), MESHDIST_MAX_CELLS, start_cell)
+
+
+def meshdist_pair_budget(m):
+    """The most (cell, face) pairs a table of m faces may list before its cell grows (include/surf_hip.h, PAIR BUDGET)."""
+    return max(MESHDIST_PAIRS_PER_FACE * m, MESHDIST_MIN_PAIR_BUDGET)
+
+
+def point_to_mesh(points, vertices, faces, max_dist=None, cell=None, stages=None, stats=None):
+    """The surf_meshdist_* rule on device tensors: points (k, 3) fp32, vertices (n, 3) fp32, faces (m, 3) int32 -> (distance (k,)
+    fp64, face (k,) int64, closest (k, 3) fp64); +inf, -1 and +inf where the distance is not < max_dist.  max_dist None: the
+    diagonal of the joint bounding box of points and vertices.  The scans, sorts and gathers between the kernels are torch's.
+    At least MESHDIST_HOST_READS reads of the device, each one small copy: (1) [smallest and largest face index, all vertices finite, all
+    points finite, the boxes of the vertices the faces name, of the points and of the vertices] before any kernel, (2) the number
+    of (cell, face) pairs, which sizes the table; read (2) is repeated once for every growth of the cell by 1.25 that the pair
+    budget asks for (none where the faces are about as large as the cells or smaller; a face that spans the table can ask for
+    several, at most log(MESHDIST_MAX_AXIS_CELLS) / log(1.25) = 38, after which the table is one cell).  Without a point and without a vertex
+    nothing is read.  A face index outside the vertex list, a vertex or a point that is not finite raise ValueError after (1).
+    cell: the cell size to use, not grown for the pair budget (tests).  stages: a list that receives (name, start event, end
+    event) per stage (pairs, sort, query); stats: a dict that receives cell, dims, pairs and max_dist."""
+    from .mesh_distance import check_max_dist, diagonal
+    _chk(points, torch.float32, "points")
+    _chk(vertices, torch.float32, "vertices")
+    _chk(faces, torch.int32, "faces")
+    if any(t.dim() != 2 or t.shape[1] != 3 for t in (points, vertices, faces)):
+        raise ValueError(f"point_to_mesh: expected (k, 3) points, (n, 3) vertices and (m, 3) faces, got {tuple(points.shape)}, "
+                         f"{tuple(vertices.shape)}, {tuple(faces.shape)}")
+    max_dist = check_max_dist(max_dist)
+    k, n, m, dev = points.shape[0], vertices.shape[0], faces.shape[0], points.device
+    if max(k, n, m) > 2 ** 31 - 1:
+        _lib.check(-2, f"point_to_mesh: {k} points / {n} vertices / {m} faces")
+    distance = torch.full((k,), float("inf"), dtype=torch.float64, device=dev)
+    face = torch.full((k,), -1, dtype=torch.int64, device=dev)
+    closest = torch.full((k, 3), float("inf"), dtype=torch.float64, device=dev)
+    if k == 0 and n == 0:
+        if m:
+            raise ValueError(f"face indices span [{int(faces.min())}, {int(faces.max())}], the mesh has 0 vertices")
+        return distance, face, closest
+
+    def stage(name):
+        if stages is not None:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            if stages:
+                stages[-1] = stages[-1][:2] + (ev,)
+            if name is not None:
+                stages.append((name, ev, None))
+
+    def box(t):                                        # [lo (3), hi (3)] as fp64, zeros for an empty tensor
+        return torch.cat([t.amin(0), t.amax(0)]).double() if t.shape[0] else torch.zeros(6, dtype=torch.float64, device=dev)
+
+    stage("pairs")
+    zero = torch.zeros(1, dtype=torch.float64, device=dev)
+    f_range = torch.stack(torch.aminmax(faces)).double() if m else torch.cat([zero, zero])
+    named = vertices[faces.reshape(-1).long().clamp_(0, max(n - 1, 0))] if m and n else vertices[:0]
+    finite = torch.stack([torch.isfinite(vertices).all(), torch.isfinite(points).all()]).double()
+    read = torch.cat([f_range, finite, box(named), box(points), box(vertices)]).tolist()                      # host read 1
+    f_lo, f_hi = int(read[0]), int(read[1])
+    if m and (f_lo < 0 or f_hi >= n):
+        raise ValueError(f"face indices span [{f_lo}, {f_hi}], the mesh has {n} vertices")
+    for ok, t, what in ((read[2], vertices, "vertex"), (read[3], points, "point")):
+        if not ok:
+            i = int(torch.nonzero(~torch.isfinite(t).all(dim=1))[0, 0])
+            raise ValueError(f"point_to_mesh: {what} {i} is not finite: {t[i].tolist()}")
+    if max_dist is None:
+        boxes = [read[10:16]] * (k > 0) + [read[16:22]] * (n > 0)
+        max_dist = diagonal([min(b[a] for b in boxes) for a in range(3)], [max(b[3 + a] for b in boxes) for a in range(3)])
+    if k == 0 or m == 0:
+        return distance, face, closest
+    L, s = _lib.lib(), _stream()
+    lo, ext = read[4:7], [b - a for a, b in zip(read[4:7], read[7:10])]
+    budget = meshdist_pair_budget(m)
+    c, dims = meshdist_cell_dims(ext, m, start_cell=cell)
+    records = torch.empty(m, 12, dtype=torch.float32, device=dev)
+    counts = torch.empty(m, dtype=torch.int64, device=dev)
+    while True:
+        L.surf_meshdist_pairs_count(_p(vertices), n, _p(faces), m, lo[0], lo[1], lo[2], c, dims[0], dims[1], dims[2], _p(records),
+                                    _p(counts), s)
+        ends = torch.cumsum(counts, 0)
+        pairs = int(ends[-1])                                                                                 # host read 2
+        if cell is not None or pairs <= budget:
+            break
+        c, dims = meshdist_cell_dims(ext, m, start_cell=1.25 * c)
+    if pairs > 2 ** 31 - 1:
+        _lib.check(-2, f"point_to_mesh: {pairs} (cell, face) pairs at the cell size {c}")
+    ncell = dims[0] * dims[1] * dims[2]
+    pair_cell = torch.empty(pairs, dtype=torch.int64, device=dev)
+    pair_face = torch.empty(pairs, dtype=torch.int32, device=dev)
+    L.surf_meshdist_pairs_emit(_p(records), m, lo[0], lo[1], lo[2], c, dims[0], dims[1], dims[2], _p(ends - counts), pairs,
+                               _p(pair_cell), _p(pair_face), s)
+    stage("sort")
+    skeys, by_cell = torch.sort(pair_cell)
+    per_cell = torch.zeros(ncell, dtype=torch.int64, device=dev).scatter_add_(0, skeys, torch.ones_like(skeys))   # (bincount reads)
+    cstart = torch.zeros(ncell + 1, dtype=torch.int32, device=dev)
+    cstart[1:] = torch.cumsum(per_cell, 0)
+    cell_records = records[pair_face[by_cell].long()].contiguous()
+    del pair_cell, pair_face, skeys, by_cell, per_cell
+    # the queries in the order of their cells (clamped to the table): speed only, the kernel writes every query's own rows
+    qc = [((points[:, a].double() - lo[a]) / c).floor_().clamp_(0.0, float(dims[a] - 1)).long() for a in range(3)]
+    order = torch.sort((qc[0] * dims[1] + qc[1]) * dims[2] + qc[2])[1]
+    stage("query")
+    L.surf_meshdist_query(_p(points), _p(order), k, _p(cell_records), pairs, _p(cstart), lo[0], lo[1], lo[2], c, dims[0], dims[1],
+                          dims[2], max_dist, _p(distance), _p(face), _p(closest), s)
+    stage(None)
+    if stats is not None:
+        stats.update(cell=c, dims=list(dims), pairs=pairs, max_dist=max_dist)
+    return distance, face, closest
+
+
+def meshdist_stats(distance):
+    """The statistics of one direction of the deviation rule from distance (k,) fp64 on the device, k >= 1: [found, largest
+    distance, S1, S2] as Python floats (the largest is -inf with nothing found), the sums by surf_smooth_sum256.  One read."""
+    _chk(distance, torch.float64, "distance")
+    L, s = _lib.lib(), _stream()
+    found = torch.isfinite(distance)
+    d = torch.where(found, distance, torch.zeros_like(distance))
+    sums = []
+    for total in (d, d * d):
+        while total.shape[0] > 1:                                      # the 256-ary sequential tree of the smoothing rule 4
+            runs = torch.empty((total.shape[0] + 255) // 256, dtype=torch.float64, device=distance.device)
+            L.surf_smooth_sum256(_p(total), total.shape[0], _p(runs), s)
+            total = runs
+        sums.append(total[0])
+    largest = torch.where(found, distance, torch.full_like(distance, float("-inf"))).max()
+    return torch.stack([found.sum().double(), largest] + sums).tolist()
+
+
+# ------------------------------------------------------------------------------------------------
 # the DTU protocol's mesh cleaner (dtu_clean.hip): elliptical dilation, rounded projection into padded masks, vertex removal
 # ------------------------------------------------------------------------------------------------
 
