@@ -724,6 +724,12 @@ int surf_band_emit(const float* vals, const int32_t* table, int res, double isov
  *   vertices (nv,3) fp32, faces (nf,3) int32 on the device; h_K (9) and h_w2c (12) HOST row-major; (h, w) the image the
  *   intrinsics refer to, (Hup, Wup) the sample lattice torch.linspace(0, w-1, Wup) x torch.linspace(0, h-1, Hup)
  *   zbuf (Hup*Wup) uint64 pre-filled with ~0: on return (depth bits << 32 | face id) of the nearest covering face
+ * Rules: coverage is inclusive (a sample on an edge or a vertex belongs to every face that has it; faces of either winding are
+ * drawn; a sample on or next to an edge that two faces share is covered by at least one of them); the nearest
+ * perspective-correct depth wins, the smaller face id on an exact tie of the fp32 depth; near rule: a face with any vertex at
+ * camera depth <= 1e-6 is not drawn at all (no near clipping); a face with a non-finite vertex or of zero screen area is
+ * ignored.  Face indices are not checked against the vertex array.  SURF_E_ARG (nothing written) for a null pointer,
+ * n_faces <= 0 or any of h, w, Hup, Wup < 2.
  */
 int surf_raster_first_hit(const float* vertices, const int32_t* faces, int64_t n_faces, const float* h_K, const float* h_w2c,
                           int h, int w, int Hup, int Wup, unsigned long long* zbuf, void* stream);
