@@ -1443,6 +1443,85 @@ int surf_meshdist_query(const float* points, const int64_t* order, int64_t k, co
                         const int32_t* cell_start, double lo_x, double lo_y, double lo_z, double cell, int64_t nx, int64_t ny,
                         int64_t nz, double max_dist, double* distance, int64_t* face, double* closest, void* stream);
 
+/*
+ * Feature-preserving mesh denoising: two-stage bilateral normal filtering (surf_amd/mesh_denoise.py, backend="device";
+ * mesh_denoise.hip).  Stage one filters the face normals (the local iterative scheme of Zheng, Fu, Au, Tai 2011, "Bilateral normal
+ * filtering for mesh denoising"), stage two moves the vertices to fit them (Sun, Rosin, Martin, Langbein 2007, "Fast and effective
+ * feature-preserving mesh denoising").  Added under SURF_ABI_VERSION 41 without a bump, like the entry points above.  The device
+ * path returns the host path's arrays: both follow the rule below, fp64 on fp32 data with separate multiplies and adds
+ * (-ffp-contract=off), one operation per operator in the written order, and no function beyond + - * / sqrt, which round
+ * correctly in numpy and on gfx950.  Faces, colours, vertex count and order never change.  "Smoothing rule k" is rule k of the
+ * surf_smooth_* group above.
+ *
+ * THE RULE.  vertices (n,3) fp32, all finite; faces (m,3) int32 with indices in [0, n); 0 <= normal_iterations, vertex_iterations
+ * <= 10000; sigma_r finite and > 0; sigma_s absent, or finite and > 0; pin_boundary; max_move absent or finite and > 0; normals
+ * not wanted, wanted, or wanted and aligned with given normals (n,3) fp32.  dot-like sums are (t0 + t1) + t2.
+ *   1. face record, from the INPUT positions p0, p1, p2 of the face's corners in order.  F = e1 x e2 by smoothing rule 5's formula
+ *      and L2 = (Fx*Fx + Fy*Fy) + Fz*Fz.  The face is DEGENERATE iff L2 == 0 or L2 is not finite, and its record is all zeros.
+ *      Otherwise L = sqrt(L2), normal[a] = (float)(F[a] / L), area = (float)(0.5 * L), centroid[a] = (float)((((double)p0[a] +
+ *      (double)p1[a]) + (double)p2[a]) / 3.0).  The normal of a face that is not degenerate has a component of at least 0.57 and
+ *      stays of unit length through rule 4, so the zero normal marks exactly the degenerate faces.
+ *   2. sigma_s when absent: the mean side length.  The side from a to b has d[a] = (double)b[a] - (double)a[a], q = (d0*d0 + d1*d1)
+ *      + d2*d2 and length sqrt(q); the 3 m lengths of the sides (p0p1, p1p2, p2p0) in (face, side) order are summed by the 256-ary
+ *      sequential tree of smoothing rule 4 and the sum is divided by (double)(3 m).  A result that is not finite or not > 0 is
+ *      refused.
+ *   3. face neighbours.  N(f) lists the faces that share at least one vertex with f, each once, f itself included, in this order:
+ *      for slot k = 0, 1, 2 of f, the corners that name vertex f[k] in (face, corner) order (corner_order / corner_start of
+ *      surf_smooth_normals); the face g of such a corner is taken unless g names one of f[0..k-1] (it was taken there), or the
+ *      corner is not g's first that names f[k] (g names the vertex twice), or f[k] equals an earlier slot of f (the slot was
+ *      walked).  Degenerate faces are members like any other: their area gives them weight 0.
+ *   4. one normal iteration (Jacobi: it reads only the normals before it; areas and centroids never change), with
+ *      is = 1.0 / (9.0 * sigma_s * sigma_s) and ir = 1.0 / (9.0 * sigma_r * sigma_r) in fp64.  A degenerate face keeps its zero
+ *      normal.  For any other f:  S = +0;  for g in N(f) in order:  d[a] = (double)c_g[a] - (double)c_f[a] of the centroids,
+ *      ds2 = (d0*d0 + d1*d1) + d2*d2, us = 1.0 - ds2 * is;  e[a] = (double)n_g[a] - (double)n_f[a] of the normals, dn2 likewise,
+ *      ur = 1.0 - dn2 * ir;  if us <= 0 or ur <= 0 the term is skipped, otherwise
+ *      w = ((double)area_g * ((us*us)*(us*us))) * ((ur*ur)*(ur*ur)) and S[a] = S[a] + w * (double)n_g[a].
+ *      L2 = (Sx*Sx + Sy*Sy) + Sz*Sz;  n'_f[a] = (float)(S[a] / sqrt(L2)), or n_f unchanged if L2 == 0 or L2 is not finite.
+ *      The weight is the compact (1 - r^2/R^2)^4 of the point-set surface with support R = 3 sigma: no exp.
+ *   5. one vertex iteration (Jacobi on fp32 positions), with n_g the normal of face g after the last normal iteration.  k_i is the
+ *      number of corners that name i and whose face is not degenerate.  x'_i = x_i to the bit if k_i == 0, or if pin_boundary and
+ *      i is a boundary vertex of smoothing rule 1.  Otherwise T = +0 and for every such corner in (face, corner) order, with
+ *      xa, xb, xc the CURRENT positions of the corners of its face g in the face's order:
+ *      c[a] = (((double)xa[a] + (double)xb[a]) + (double)xc[a]) / 3.0 (not rounded to fp32),
+ *      d = ((c0 - x0)*n0 + (c1 - x1)*n1) + (c2 - x2)*n2 with x = (double)x_i and n = (double)n_g,  T[a] = T[a] + n[a] * d;
+ *      x'_i[a] = (float)((double)x_i[a] + T[a] / (double)k_i).  A face that names i twice is added twice.
+ *   6. displacement cap, movement statistics and normals: smoothing rules 4 and 5 verbatim, through surf_smooth_cap,
+ *      surf_smooth_sum256 and surf_smooth_normals; the boundary flags are surf_smooth_adjacency's.
+ * Fixed points: a mesh whose faces around every moving vertex lie in one plane has d == 0 in rule 5 wherever c - x lies in that
+ * plane to the bit (a lattice cube, a planar grid), and a neighbourhood of equal normals returns that normal from rule 4 when the
+ * normalisation is exact; the tests pin both on a cube and on a planar grid.
+ *
+ * Entry points, in the order surf_amd.ops.denoise_mesh calls them (sorts, scans and searches between them are the caller's).
+ * Face records travel as (m,8) fp32 rows of 32 bytes, (nx, ny, nz, area, cx, cy, cz, unused): two 16-byte loads, the first of
+ * which is all a normal iteration writes; positions travel as (n,4) fp32 rows as in smoothing.
+ *   surf_denoise_face_records: rule 1 into records (m,8), and when side_lengths is not null rule 2's (m,3) fp64 lengths.  A face
+ *     with an index outside [0, n) gets a zero record and zero lengths (the caller has refused such faces before).
+ *   surf_denoise_neighbour_count: counts (m) int64 = the length of N(f).  corner_order (3 m) int64, corner_start (n + 1) int64 as
+ *     for surf_smooth_normals.  The caller scans them: face_row_start (m + 1) int32 with the total last, which it READS first:
+ *   surf_denoise_neighbour_emit: face_neighbours (total) int32 = N(f) row after row.  total > 2^31 - 1 is SURF_E_LIMIT, here and in
+ *     the caller, before anything is written.
+ *   surf_denoise_normal_step: rule 4, the first 16 bytes of every row of records_out from records_in (both hold the same areas
+ *     and centroids).  One face per lane; a row of more than SURF_DENOISE_WAVE_ROW neighbours is summed by the face's whole
+ *     wavefront, 64 gathers at a time, in the same order.
+ *   surf_denoise_vertex_step: rule 5, positions_out from positions_in and the normals of records.  One vertex per lane; a vertex
+ *     of more than SURF_DENOISE_WAVE_ROW corners is summed by its whole wavefront in the same way.
+ * n == 0 or m == 0 returns 0 at once.  n or m > SURF_SMOOTH_MAX_ITEMS and total > 2^31 - 1 are SURF_E_LIMIT; a null pointer, a
+ * negative size, in == out and an is or ir that is not finite and >= 0 are SURF_E_ARG; all reported before any launch.
+ */
+#define SURF_DENOISE_WAVE_ROW 48
+int surf_denoise_face_records(const float* vertices, int64_t n, const int32_t* faces, int64_t m, float* records,
+                              double* side_lengths, void* stream);
+int surf_denoise_neighbour_count(const int32_t* faces, int64_t m, int64_t n, const int64_t* corner_order,
+                                 const int64_t* corner_start, int64_t* counts, void* stream);
+int surf_denoise_neighbour_emit(const int32_t* faces, int64_t m, int64_t n, const int64_t* corner_order,
+                                const int64_t* corner_start, const int32_t* face_row_start, int64_t total,
+                                int32_t* face_neighbours, void* stream);
+int surf_denoise_normal_step(const float* records_in, float* records_out, int64_t m, const int32_t* face_row_start,
+                             const int32_t* face_neighbours, int64_t total, double inv_s, double inv_r, void* stream);
+int surf_denoise_vertex_step(const float* positions_in, float* positions_out, int64_t n, const int32_t* faces, int64_t m,
+                             const float* records, const int64_t* corner_order, const int64_t* corner_start,
+                             const uint8_t* boundary, int pin_boundary, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

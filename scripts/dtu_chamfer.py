@@ -70,6 +70,19 @@ def parse_args(argv=None):
     ap.add_argument("--vertex_colors", action="store_true",
                     help="also write per-vertex normals (nx ny nz) and blended colours (red green blue) into the PLY "
                          "(ImplicitSurface.vertex_attributes on the final vertex set; geometry and Chamfer unchanged)")
+    ap.add_argument("--denoise_iters", type=int, default=None, metavar="N",
+                    help="denoise the mesh and keep its edges: N bilateral filter passes over the face normals, then vertex passes "
+                         "that fit them (surf_amd/mesh_denoise.py) after --clean_mesh and before --smooth_iters and "
+                         "--simplify_cell; with --vertex_colors the normals are recomputed, on the side of the ones they replace")
+    ap.add_argument("--denoise_vertex_iters", type=int, default=10, metavar="N", help="vertex passes after the normal passes")
+    ap.add_argument("--denoise_sigma_r", type=float, default=0.35,
+                    help="normals further apart than 3 of these (as a chord of the unit sphere) do not average each other")
+    ap.add_argument("--denoise_sigma_s", type=float, default=None,
+                    help="the same for the distance of two face centroids, in the mesh's own units; default: the mean side length")
+    ap.add_argument("--denoise_max_move", type=float, default=None,
+                    help="no vertex ends further than this from where it started, in the mesh's own units (the normalised frame)")
+    ap.add_argument("--denoise_free_boundary", action="store_true", help="let the vertices on open edges move too (default: pinned)")
+    ap.add_argument("--denoise_backend", default="host", choices=["host", "device"])
     ap.add_argument("--smooth_iters", type=int, default=None, metavar="N",
                     help="smooth the mesh with N Taubin lambda|mu pairs (surf_amd/mesh_smooth.py) after --clean_mesh and before "
                          "--simplify_cell; with --vertex_colors the normals are recomputed from the smoothed mesh, on the side of "
@@ -105,6 +118,22 @@ def parse_args(argv=None):
     return ap.parse_args(argv)
 
 
+def denoise_params(args):
+    """The --denoise_* flags as mesh_denoise's argument dict, or None without --denoise_iters (a Namespace built by hand may lack
+    them)."""
+    iters = getattr(args, "denoise_iters", None)
+    if iters is None:
+        return None
+    from surf_amd.mesh_denoise import check_params
+    try:
+        return check_params({"normal_iterations": iters, "vertex_iterations": getattr(args, "denoise_vertex_iters", 10),
+                             "sigma_r": getattr(args, "denoise_sigma_r", 0.35), "sigma_s": getattr(args, "denoise_sigma_s", None),
+                             "pin_boundary": not getattr(args, "denoise_free_boundary", False),
+                             "max_move": getattr(args, "denoise_max_move", None)})
+    except ValueError as e:
+        raise SystemExit(f"dtu_chamfer: {e}")
+
+
 def run(args, state=None):
     """Returns the JSON record.  state (dict, tests): receives the live `model`, the loader's `item` and the final normalised-frame
     `vertices` / `triangles` of the (last) evaluation."""
@@ -130,9 +159,11 @@ def run(args, state=None):
                                    "pin_boundary": not args.smooth_free_boundary, "max_move": args.smooth_max_move})
         except ValueError as e:
             raise SystemExit(f"dtu_chamfer: {e}")
+    denoise = denoise_params(args)
     deviation = bool(getattr(args, "deviation", False))
-    if deviation and smooth is None and args.simplify_cell is None:
-        raise SystemExit("dtu_chamfer: --deviation compares the mesh before and after --smooth_iters / --simplify_cell: give one of them")
+    if deviation and smooth is None and denoise is None and args.simplify_cell is None:
+        raise SystemExit("dtu_chamfer: --deviation compares the mesh before and after --denoise_iters / --smooth_iters / "
+                         "--simplify_cell: give one of them")
     cfg = C.parse_file(args.conf)
     dconf = cfg["val_dataset"]
     if args.data_dir is not None:
@@ -193,7 +224,15 @@ def run(args, state=None):
         os.makedirs(os.path.dirname(mesh_path), exist_ok=True)
         if state is not None:
             state.update(model=model, item=item, vertices=v, triangles=t)
-        attrs, t_attr, simplified, smoothed = {}, None, None, None
+        attrs, t_attr, simplified, smoothed, denoised = {}, None, None, None, None
+
+        def denoise_now(v, normals):                 # in the normalised frame, before the smoothing and the simplification
+            from surf_amd.mesh_denoise import denoise_step
+            try:
+                return denoise_step(v, t, denoise, normals=normals, backend=getattr(args, "denoise_backend", "host"), device=dev)
+            except ValueError as e:
+                raise SystemExit(f"dtu_chamfer: {e}")
+
         if args.vertex_colors:                   # on the final vertex set: after clean_mesh, before scale_mat
             t0 = time.perf_counter()
             attrs = model.vertex_attributes(v)
@@ -209,6 +248,9 @@ def run(args, state=None):
             normals, colors = attrs.get("normals"), attrs.get("colors")
             normals, colors = (None if normals is None else normals[kept]), (None if colors is None else colors[kept])
             before = (v, t)                      # mesh A of --deviation: after the cleaner, before the steps it measures
+            if denoise is not None:
+                v, normals, denoised = denoise_now(v, normals)
+                vw = mesh_io.transform_vertices(v, scale_mat)
             if smooth is not None:               # in the normalised frame, like the simplification; the world-frame vertices follow
                 v, normals, smoothed = smooth_step(v, t, smooth, normals=normals, backend=args.smooth_backend, device=dev)
                 vw = mesh_io.transform_vertices(v, scale_mat)
@@ -223,6 +265,10 @@ def run(args, state=None):
         else:
             normals, colors = attrs.get("normals"), attrs.get("colors")
             before = (v, t)
+            if denoise is not None:
+                v, normals, denoised = denoise_now(v, normals)
+                if state is not None:
+                    state.update(vertices=v, triangles=t)
             if smooth is not None:
                 v, normals, smoothed = smooth_step(v, t, smooth, normals=normals, backend=args.smooth_backend, device=dev)
                 if state is not None:
@@ -256,7 +302,7 @@ def run(args, state=None):
                 "clean_backend": args.clean_backend if args.clean_mesh else None, "clean_protocol": protocol,
                 "seconds": {"load": t_load, "val_forward": t_val, "clean": t_clean, "evaluate": t_eval,
                             **({} if t_attr is None else {"vertex_attributes": t_attr})},
-                **({} if smoothed is None else {"smooth": smoothed}), **({} if simplified is None else {"simplify": simplified}),
+                **({} if denoised is None else {"denoise": denoised}), **({} if smoothed is None else {"smooth": smoothed}), **({} if simplified is None else {"simplify": simplified}),
                 **({} if deviated is None else {"deviation": deviated})}
 
     if not args.sweep:

@@ -28,7 +28,13 @@ With --smooth_iters N [--smooth_lambda L --smooth_mu M | --smooth_laplacian] [--
 mesh is smoothed (surf_amd/mesh_smooth.py, csrc/mesh_smooth.hip: N Taubin lambda|mu pairs, or N Laplacian steps) after --clean_mesh
 and before --simplify_mm; positions move, faces and colours stay; the record gains `smooth` {iterations, lam, mu, pin_boundary,
 max_move, vertices, boundary_vertices, isolated_vertices, moved_max, moved_rms, capped, ms}.  --cloud_mesh is smoothed the same way.
-With --deviation [--deviation_backend device] [--deviation_max_mm X] (needs --smooth_iters or --simplify_mm) the record gains
+With --denoise_iters N [--denoise_vertex_iters N --denoise_sigma_r X --denoise_sigma_s_mm X --denoise_max_move_mm X
+--denoise_free_boundary --denoise_backend device] the mesh is denoised with its edges kept (surf_amd/mesh_denoise.py,
+csrc/mesh_denoise.hip: N bilateral passes over the face normals, then vertex passes that fit them) after --clean_mesh and before
+--smooth_iters and --simplify_mm; the record gains `denoise` {normal_iterations, vertex_iterations, sigma_r, sigma_s, pin_boundary,
+max_move, vertices, faces, degenerate_faces, boundary_vertices, moved_max, moved_rms, capped, ms}.  --cloud_mesh is denoised the
+same way.
+With --deviation [--deviation_backend device] [--deviation_max_mm X] (needs --denoise_iters, --smooth_iters or --simplify_mm) the record gains
 `deviation` {forward, backward, hausdorff, max_dist, ms}: the vertex-sampled deviation (surf_amd/mesh_distance.py, exact
 point-to-triangle distances) between the mesh after --clean_mesh and the mesh that is written; with --cloud_mesh the `cloud_mesh`
 block gains the same `deviation` for the cloud mesh (its surface is extracted a second time without the mesh steps).
@@ -117,6 +123,19 @@ def parse_args(argv=None):
     ap.add_argument("--dtu_test_dir", default=None, help="DTU_TEST tree (cameras/, scan<N>/mask/) of --clean_mesh")
     ap.add_argument("--clean_set", type=int, default=1, choices=[0, 1], help="view set of --clean_mesh")
     ap.add_argument("--clean_backend", default="host", choices=["host", "device"])
+    ap.add_argument("--denoise_iters", type=int, default=None, metavar="N",
+                    help="denoise the mesh and keep its edges: N bilateral filter passes over the face normals, then vertex passes "
+                         "that fit them (surf_amd/mesh_denoise.py): after --clean_mesh, before --smooth_iters and --simplify_mm; "
+                         "also applied to --cloud_mesh")
+    ap.add_argument("--denoise_vertex_iters", type=int, default=10, metavar="N", help="vertex passes after the normal passes")
+    ap.add_argument("--denoise_sigma_r", type=float, default=0.35,
+                    help="normals further apart than 3 of these (as a chord of the unit sphere) do not average each other")
+    ap.add_argument("--denoise_sigma_s_mm", type=float, default=None,
+                    help="the same for the distance of two face centroids (world units; DTU: millimetres); default: the mean side length")
+    ap.add_argument("--denoise_max_move_mm", type=float, default=None,
+                    help="no vertex ends further than this from where it started (world units; DTU: millimetres)")
+    ap.add_argument("--denoise_free_boundary", action="store_true", help="let the vertices on open edges move too (default: pinned)")
+    ap.add_argument("--denoise_backend", default="host", choices=["host", "device"])
     ap.add_argument("--smooth_iters", type=int, default=None, metavar="N",
                     help="smooth the mesh with N Taubin lambda|mu pairs (surf_amd/mesh_smooth.py): after --clean_mesh, before "
                          "--simplify_mm; also applied to --cloud_mesh")
@@ -161,6 +180,22 @@ def parse_args(argv=None):
     return ap.parse_args(argv)
 
 
+def denoise_params(args):
+    """The --denoise_* flags as mesh_denoise's argument dict, or None without --denoise_iters (a Namespace built by hand may lack
+    them)."""
+    iters = getattr(args, "denoise_iters", None)
+    if iters is None:
+        return None
+    from surf_amd.mesh_denoise import check_params
+    try:
+        return check_params({"normal_iterations": iters, "vertex_iterations": getattr(args, "denoise_vertex_iters", 10),
+                             "sigma_r": getattr(args, "denoise_sigma_r", 0.35), "sigma_s": getattr(args, "denoise_sigma_s_mm", None),
+                             "pin_boundary": not getattr(args, "denoise_free_boundary", False),
+                             "max_move": getattr(args, "denoise_max_move_mm", None)})
+    except ValueError as e:
+        raise SystemExit(f"fuse_scene: {e}")
+
+
 def smooth_params(args):
     """The --smooth_* flags as mesh_smooth's argument dict, or None without --smooth_iters (a Namespace built by hand may lack them)."""
     iters = getattr(args, "smooth_iters", None)
@@ -174,6 +209,29 @@ def smooth_params(args):
                              "max_move": getattr(args, "smooth_max_move_mm", None)})
     except ValueError as e:
         raise SystemExit(f"fuse_scene: {e}")
+
+
+def mesh_steps(v, t, colors, args, denoise, smooth, dev):
+    """The mesh steps after the cleaner, in their order - denoise, smooth, simplify - each only if asked for: (vertices, triangles,
+    colors, denoise record, smooth record, simplify record), a record None for a step that did not run."""
+    denoised = None
+    if denoise is not None:                             # after the cleaner, before the filter that rounds what this one keeps
+        from surf_amd.mesh_denoise import denoise_step
+        try:
+            v, _, denoised = denoise_step(v, t, denoise, backend=getattr(args, "denoise_backend", "host"), device=dev)
+        except ValueError as e:
+            raise SystemExit(f"fuse_scene: {e}")
+    smoothed = None
+    if smooth is not None:                              # after the cleaner, whose masks are about the measured surface
+        from surf_amd.mesh_smooth import smooth_step
+        v, _, smoothed = smooth_step(v, t, smooth, backend=getattr(args, "smooth_backend", "host"), device=dev)
+    simplified = None
+    if args.simplify_mm is not None:                    # the last mesh step: the cleaner's component threshold is about the full mesh
+        from surf_amd.mesh_simplify import simplify_step
+        v, t, _, colors, simplified = simplify_step(v, t, args.simplify_mm, colors=colors, backend=args.simplify_backend, device=dev)
+        if len(t) == 0:
+            raise SystemExit(f"fuse_scene: --simplify_mm {args.simplify_mm} leaves no face (the cell swallows the mesh)")
+    return v, t, colors, denoised, smoothed, simplified
 
 
 def run(args, state=None):
@@ -210,9 +268,11 @@ def run(args, state=None):
     if cloud_mesh and not (args.point_cloud and cloud_normals is not None):
         raise SystemExit("fuse_scene: --cloud_mesh needs --point_cloud and --cloud_normals (the surface is taken from oriented points)")
     smooth = smooth_params(args)
+    denoise = denoise_params(args)
     deviation = bool(getattr(args, "deviation", False))
-    if deviation and smooth is None and args.simplify_mm is None:
-        raise SystemExit("fuse_scene: --deviation compares the mesh before and after --smooth_iters / --simplify_mm: give one of them")
+    if deviation and smooth is None and denoise is None and args.simplify_mm is None:
+        raise SystemExit("fuse_scene: --deviation compares the mesh before and after --denoise_iters / --smooth_iters / --simplify_mm: "
+                         "give one of them")
     cfg = C.parse_file(args.conf)
     dconf = cfg["val_dataset"]
     if args.data_dir is not None:
@@ -308,7 +368,7 @@ def run(args, state=None):
                 radius = float(getattr(args, "cloud_mesh_radius", 3.0)) * voxel
                 min_points = int(getattr(args, "cloud_mesh_min_points", 4))
                 cm = point_surface.reconstruct(cloud, cloud_nrm, voxel, radius=radius, min_points=min_points, bounds=(lo, hi),
-                                               simplify_cell=args.simplify_mm, device=dev, stats=st, smooth=smooth)
+                                               simplify_cell=args.simplify_mm, device=dev, stats=st, smooth=smooth, denoise=denoise)
                 if len(cm[1]) == 0:
                     raise SystemExit("fuse_scene: --cloud_mesh found no zero crossing between observed lattice points (empty mesh)")
                 cloud_deviated = None
@@ -369,16 +429,7 @@ def run(args, state=None):
         colors = None if colors is None else colors[kept]
         ms["clean"] = 1e3 * (time.perf_counter() - t0)
     before = (v, t) if deviation else None              # mesh A of --deviation: after the cleaner, before the steps it measures
-    smoothed = None
-    if smooth is not None:                              # after the cleaner, whose masks are about the measured surface
-        from surf_amd.mesh_smooth import smooth_step
-        v, _, smoothed = smooth_step(v, t, smooth, backend=getattr(args, "smooth_backend", "host"), device=dev)
-    simplified = None
-    if args.simplify_mm is not None:                    # the last mesh step: the cleaner's component threshold is about the full mesh
-        from surf_amd.mesh_simplify import simplify_step
-        v, t, _, colors, simplified = simplify_step(v, t, args.simplify_mm, colors=colors, backend=args.simplify_backend, device=dev)
-        if len(t) == 0:
-            raise SystemExit(f"fuse_scene: --simplify_mm {args.simplify_mm} leaves no face (the cell swallows the mesh)")
+    v, t, colors, denoised, smoothed, simplified = mesh_steps(v, t, colors, args, denoise, smooth, dev)
     deviated = None
     if before is not None:                              # mesh B is the mesh that is written
         from surf_amd.mesh_distance import deviation_step
@@ -428,6 +479,8 @@ def run(args, state=None):
            "colors": bool(args.colors), "cleaned": bool(args.clean_mesh), "mesh": mesh_path, "ms": ms}
     if args.sparse:                                     # without the flag the record is what it was
         rec.update(sparse=True, bricks=volume.n_bricks, allocated_share=volume.allocated_share(), state_bytes=volume.state_bytes())
+    if denoised is not None:                            # without the flag the record is what it was
+        rec.update(denoise=denoised)
     if smoothed is not None:                            # without the flag the record is what it was
         rec.update(smooth=smoothed)
     if simplified is not None:                          # without the flag the record is what it was

@@ -748,7 +748,7 @@ class FusionVolume:
         """Share of the lattice points that at least one view updated."""
         return float((self.weight > 0).sum()) / float(np.prod(self.shape))
 
-    def extract_mesh(self, isovalue=0.0, simplify_cell=None, smooth=None):
+    def extract_mesh(self, isovalue=0.0, simplify_cell=None, smooth=None, denoise=None):
         """(vertices (V, 3) float64 in the world frame, triangles (F, 3) int64[, colors (V, 3) uint8 when colours are fused]) as
         numpy arrays: marching cubes at u = -tsdf = isovalue over the cells whose eight corners were observed, one copy to the
         host.  Runs on the GPU whatever the backend (the host backend's state is uploaded).
@@ -757,7 +757,10 @@ class FusionVolume:
         positions are then fp32 values.
         smooth (a dict of mesh_smooth.smooth_mesh's iterations, lam, mu, pin_boundary, max_move; {} for the defaults): the mesh is
         smoothed first - mesh_smooth.smooth_mesh of exactly the arrays that smooth=None returns, by the volume's backend, before
-        simplify_cell is applied; positions are then fp32 values."""
+        simplify_cell is applied; positions are then fp32 values.
+        denoise (a dict of mesh_denoise.denoise_mesh's normal_iterations, vertex_iterations, sigma_r, sigma_s, pin_boundary,
+        max_move; {} for the defaults): the mesh is denoised before anything else - mesh_denoise.denoise_mesh of exactly the arrays
+        that denoise=None returns, by the volume's backend; smooth and simplify_cell then apply to the denoised mesh."""
         if self.backend == "device":
             dev, tsdf, weight, color, axes = self.device, self.tsdf, self.weight, self.color, self.axes
         else:
@@ -769,7 +772,7 @@ class FusionVolume:
             axes = [torch.from_numpy(a).to(dev) for a in self.axes]
         v, t = ops.marching_cubes(ops.fuse_lattice(tsdf, weight), float(isovalue), observed_only=True)
         c = None if color is None else ops.fuse_vertex_colors(v, color)
-        return self._finished(v, t, c, axes, simplify_cell, smooth)
+        return self._finished(v, t, c, axes, simplify_cell, smooth, denoise)
 
     def lattice(self):
         """(lo (3,) float64, voxel) of a uniform lattice: the (lo, hi, voxel) it was built from, or what its coordinate arrays
@@ -842,17 +845,21 @@ class FusionVolume:
             cols.append(ax[lo] + (ax[hi] - ax[lo]) * (v[:, a] - lo.double()))
         return torch.stack(cols, dim=1) if len(v) else v
 
-    def _finished(self, v, t, c, axes, cell, smooth):
-        """extract_mesh's arrays of the device mesh (v in lattice-index units), smoothed if `smooth` is given, then simplified if
-        `cell` is.  Device backend: both on the device, one copy of the final mesh; host backend: the numpy paths on the full
-        mesh's host arrays."""
-        if cell is None and smooth is None:
+    def _finished(self, v, t, c, axes, cell, smooth, denoise=None):
+        """extract_mesh's arrays of the device mesh (v in lattice-index units), denoised if `denoise` is given, smoothed if
+        `smooth` is, then simplified if `cell` is.  Device backend: all on the device, one copy of the final mesh; host backend:
+        the numpy paths on the full mesh's host arrays."""
+        if cell is None and smooth is None and denoise is None:
             return self._mesh_to_host(v, t, c, axes)
+        from . import mesh_denoise
         from .mesh_simplify import simplify_mesh
         from .mesh_smooth import check_params, smooth_mesh
         params = None if smooth is None else check_params(smooth)
+        dparams = None if denoise is None else mesh_denoise.check_params(denoise)
         if self.backend == "device":
             out = [self._world(v, axes), t] + ([] if c is None else [c])
+            if dparams is not None and len(v):
+                out[0] = mesh_denoise.denoise_mesh(out[0], t, backend="device", device=v.device, return_tensors=True, **dparams)[0]
             if params is not None and len(v):
                 out[0] = smooth_mesh(out[0], t, backend="device", device=v.device, return_tensors=True, **params)[0]
             if cell is not None:
@@ -860,6 +867,8 @@ class FusionVolume:
             out = [to_host(x).numpy() for x in out]
         else:
             out = list(self._mesh_to_host(v, t, c, axes))
+            if dparams is not None and len(out[0]):
+                out[0] = mesh_denoise.denoise_mesh(out[0], out[1], backend="host", **dparams)[0]
             if params is not None and len(out[0]):
                 out[0] = smooth_mesh(out[0], out[1], backend="host", **params)[0]
             if cell is not None:
@@ -1053,10 +1062,10 @@ class SparseFusionVolume(FusionVolume):
         bricks, table, tsdf, weight, color = self.finalize()._state
         return tsdf, weight, color, table, self.n_bricks > 0
 
-    def extract_mesh(self, isovalue=0.0, simplify_cell=None, smooth=None):
+    def extract_mesh(self, isovalue=0.0, simplify_cell=None, smooth=None, denoise=None):
         """FusionVolume.extract_mesh's arrays, the same mesh in the same order, for -1 < isovalue < 1 (ValueError otherwise: the
-        allocation covers only what such an isovalue can cut).  Runs on the GPU whatever the backend.  simplify_cell, smooth: as
-        there."""
+        allocation covers only what such an isovalue can cut).  Runs on the GPU whatever the backend.  simplify_cell, smooth,
+        denoise: as there."""
         if not -1.0 < float(isovalue) < 1.0:
             raise ValueError("FusionVolume(sparse=True).extract_mesh: -1 < isovalue < 1")
         self.finalize()
@@ -1075,4 +1084,4 @@ class SparseFusionVolume(FusionVolume):
         band = ops.Band(self.res, table, None, bricks, ops.fuse_band_values(tsdf, weight), {}, shape=self.shape)
         v, t = ops.marching_cubes_band(band, float(isovalue), observed_only=True)
         c = None if color is None else ops.fuse_vertex_colors_bricks(v, color, table, self.shape)
-        return self._finished(v, t, c, axes, simplify_cell, smooth)
+        return self._finished(v, t, c, axes, simplify_cell, smooth, denoise)

@@ -8,7 +8,8 @@ which adds its terms one after the other in the order given - ascending neighbou
 normals.  backend="device" runs csrc/mesh_smooth.hip through surf_amd.ops.smooth_mesh and returns the same arrays; it has no host
 fall-back.
 
-Not attempted: cotangent weights, bilateral and other feature-preserving filters, implicit solves, remeshing."""
+The umbrella operator rounds edges and corners; surf_amd/mesh_denoise.py is the filter that keeps them (bilateral normal filtering).
+Not attempted: cotangent weights, implicit solves, remeshing."""
 import math
 import time
 

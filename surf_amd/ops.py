@@ -1974,6 +1974,156 @@ def smooth_mesh(vertices, faces, iterations=10, lam=0.5, mu=-0.53, pin_boundary=
 
 
 # ------------------------------------------------------------------------------------------------
+# mesh denoising (mesh_denoise.hip): two-stage bilateral normal filtering; the rule is in include/surf_hip.h
+# ------------------------------------------------------------------------------------------------
+
+DENOISE_HOST_READS = 3           # denoise_mesh waits for the device three times: see its docstring
+
+
+def _sum256(values):
+    """The 256-ary sequential tree of smoothing rule 4 over a device tensor of fp64 values (at least one): a 1-element tensor."""
+    L, s, total = _lib.lib(), _stream(), values
+    while total.shape[0] > 1:
+        runs = torch.empty((total.shape[0] + 255) // 256, dtype=torch.float64, device=values.device)
+        L.surf_smooth_sum256(_p(total), total.shape[0], _p(runs), s)
+        total = runs
+    return total
+
+
+def denoise_corners(faces, n):
+    """(corner_order (3 m) int64, corner_start (n + 1) int64) of device faces (m, 3) int32, as surf_smooth_normals takes them."""
+    sorted_v, corder = torch.sort(faces.reshape(-1), stable=True)      # stable: a vertex lists its corners in (face, corner) order
+    cstart = torch.searchsorted(sorted_v, torch.arange(n + 1, dtype=torch.int32, device=faces.device))
+    return corder, cstart
+
+
+def denoise_neighbours(faces, n, corners=None, also=()):
+    """Rule 3 of the surf_denoise_* group on a device tensor faces (m, 3) int32 with valid indices, m, n >= 1: (face_row_start
+    (m + 1) int32, face_neighbours (total) int32, values of `also`).  One read of the device: the total and the 0-dim tensors of
+    `also`; a total above 2^31 - 1 raises SurfHipError after it, before the list is allocated."""
+    from .mesh_denoise import MAX_NEIGHBOURS
+    _chk(faces, torch.int32, "faces")
+    m, dev = faces.shape[0], faces.device
+    if max(n, m) > SMOOTH_MAX_ITEMS:
+        _lib.check(-2, f"denoise_mesh: {n} vertices / {m} faces")
+    L, s = _lib.lib(), _stream()
+    corder, cstart = denoise_corners(faces, n) if corners is None else corners
+    counts = torch.empty(m, dtype=torch.int64, device=dev)
+    L.surf_denoise_neighbour_count(_p(faces), m, n, _p(corder), _p(cstart), _p(counts), s)
+    rows = torch.zeros(m + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, out=rows[1:])
+    read = torch.stack([rows[m].double()] + [t.double() for t in also]).tolist()                              # host read
+    total = int(read[0])
+    if total > MAX_NEIGHBOURS:
+        _lib.check(-2, f"denoise_mesh: {total} face neighbours")
+    rows = rows.to(torch.int32)
+    nbr = torch.empty(total, dtype=torch.int32, device=dev)
+    L.surf_denoise_neighbour_emit(_p(faces), m, n, _p(corder), _p(cstart), _p(rows), total, _p(nbr), s)
+    return rows, nbr, read[1:]
+
+
+def denoise_mesh(vertices, faces, normal_iterations=10, vertex_iterations=10, sigma_r=0.35, sigma_s=None, pin_boundary=True,
+                 max_move=None, normals=None, stages=None, keep=None):
+    """The surf_denoise_* rule on device tensors: vertices (n, 3) fp32, faces (m, 3) int32, normals None, True or (n, 3) fp32 ->
+    (vertices (n, 3) fp32, normals (n, 3) fp32 or None, info); the arguments and info are surf_amd.mesh_denoise.denoise_mesh's.
+    The sorts, scans and searches between the kernels are torch's.  At most DENOISE_HOST_READS reads of the device, each one small
+    copy: (1) smooth_adjacency's [neighbour entries, smallest and largest face index, all vertices finite], (2) [face neighbour
+    total, summed side lengths] when there is a normal iteration or sigma_s is absent, (3) [boundary vertices, degenerate faces,
+    largest and summed squared movement, capped vertices] for info; an empty mesh reads nothing.  A face index outside the vertex
+    list or a vertex that is not finite raises ValueError after (1), a mean side length that is not > 0 after (2).
+    stages: a list that receives (name, start event, end event) per stage (scripts/time_mesh_denoise.py).  keep: a dict that
+    receives the tensors face_row_start, face_neighbours (when there is a normal iteration) and records (m, 8) after the normal
+    stage."""
+    from .mesh_denoise import check_args, inverse_supports, mean_side
+    _chk(vertices, torch.float32, "vertices")
+    _chk(faces, torch.int32, "faces")
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"denoise_mesh: expected (n, 3) vertices and (m, 3) faces, got {tuple(vertices.shape)}, {tuple(faces.shape)}")
+    normal_iterations, vertex_iterations, sigma_r, sigma_s, pin_boundary, max_move = check_args(
+        normal_iterations, vertex_iterations, sigma_r, sigma_s, pin_boundary, max_move)
+    n, m, dev = vertices.shape[0], faces.shape[0], vertices.device
+    if max(n, m) > SMOOTH_MAX_ITEMS:
+        _lib.check(-2, f"denoise_mesh: {n} vertices / {m} faces")
+    given = None if normals is None or normals is True else normals
+    if given is not None:
+        _chk(given, torch.float32, "normals")
+        if tuple(given.shape) != (n, 3):
+            raise ValueError(f"denoise_mesh: normals {tuple(given.shape)} for {n} vertices")
+    if n == 0 or m == 0:
+        nrm = given if given is not None else (torch.zeros(n, 3, dtype=torch.float32, device=dev) if normals is True else None)
+        return vertices, nrm, {"vertices": n, "faces": m, "degenerate_faces": 0, "boundary_vertices": 0, "sigma_s": sigma_s,
+                               "sigma_r": sigma_r, "moved_max": 0.0, "moved_rms": 0.0, "capped": 0}
+
+    def stage(name):
+        if stages is not None:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            if stages:
+                stages[-1] = stages[-1][:2] + (ev,)
+            if name is not None:
+                stages.append((name, ev, None))
+
+    L, s = _lib.lib(), _stream()
+    stage("adjacency")
+    _, _, boundary, (finite,) = smooth_adjacency(faces, n, also=(torch.isfinite(vertices).all(),))           # host read 1
+    if not finite:
+        i = int(torch.nonzero(~torch.isfinite(vertices).all(dim=1))[0, 0])
+        raise ValueError(f"denoise_mesh: vertex {i} is not finite: {vertices[i].tolist()}")
+    stage("records")
+    corners = denoise_corners(faces, n)
+    records = torch.empty(m, 8, dtype=torch.float32, device=dev)
+    sides = torch.empty(m, 3, dtype=torch.float64, device=dev) if sigma_s is None else None
+    L.surf_denoise_face_records(_p(vertices), n, _p(faces), m, _p(records), _p(sides), s)
+    also = () if sides is None else (_sum256(sides.reshape(-1))[0],)
+    rows = nbr = None
+    if normal_iterations:
+        stage("neighbours")
+        rows, nbr, read = denoise_neighbours(faces, n, corners, also)                                         # host read 2
+    else:
+        read = torch.stack(list(also)).tolist() if also else []                                               # host read 2
+    if sigma_s is None:
+        sigma_s = mean_side(read[0], m)
+    inv_s, inv_r = inverse_supports(sigma_s, sigma_r)
+    if normal_iterations:
+        stage("normal_steps")
+        other = records.clone()                                        # areas and centroids in both buffers
+        for _ in range(normal_iterations):
+            L.surf_denoise_normal_step(_p(records), _p(other), m, _p(rows), _p(nbr), nbr.shape[0], inv_s, inv_r, s)
+            records, other = other, records
+        del other
+    if keep is not None:
+        keep.update(records=records)
+        if rows is not None:
+            keep.update(face_row_start=rows, face_neighbours=nbr)
+    stage("vertex_steps")
+    a = torch.zeros(n, 4, dtype=torch.float32, device=dev)             # 16-byte rows: a corner's position is one load
+    a[:, :3] = vertices
+    if vertex_iterations:
+        b = torch.empty_like(a)
+        for _ in range(vertex_iterations):
+            L.surf_denoise_vertex_step(_p(a), _p(b), n, _p(faces), m, _p(records), _p(corners[0]), _p(corners[1]), _p(boundary),
+                                       int(pin_boundary), s)
+            a, b = b, a
+    stage("cap")
+    out = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    moved2 = torch.empty(n, dtype=torch.float64, device=dev)
+    capped = torch.empty(n, dtype=torch.uint8, device=dev)
+    L.surf_smooth_cap(_p(a), _p(vertices), n, 0.0 if max_move is None else max_move, _p(out), _p(moved2), _p(capped), s)
+    total = _sum256(moved2)
+    nrm = None
+    if normals is not None:
+        stage("normals")
+        nrm = smooth_normals(out, faces, given)
+    stage(None)
+    degenerate = (records[:, :3] == 0).all(dim=1).sum()
+    nb, nd, qmax, qsum, nc = torch.stack([boundary.sum().double(), degenerate.double(), moved2.max(), total[0],
+                                          capped.sum().double()]).tolist()                                   # host read 3
+    info = {"vertices": n, "faces": m, "degenerate_faces": int(nd), "boundary_vertices": int(nb), "sigma_s": sigma_s,
+            "sigma_r": sigma_r, "moved_max": float(np.sqrt(qmax)), "moved_rms": float(np.sqrt(qsum / float(n))), "capped": int(nc)}
+    return out, nrm, info
+
+
+# ------------------------------------------------------------------------------------------------
 # mesh deviation (mesh_distance.hip): exact point-to-triangle distances; the rule is in include/surf_hip.h
 # ------------------------------------------------------------------------------------------------
 

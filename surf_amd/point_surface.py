@@ -279,11 +279,11 @@ def cloud_bounds(points, normals, radius):
 
 @torch.no_grad()
 def reconstruct(cloud, normals, voxel, radius=None, min_points=4, bounds=None, colors=None, simplify_cell=None, backend="device",
-                device=None, stats=None, smooth=None):
+                device=None, stats=None, smooth=None, denoise=None):
     """(vertices (V, 3) float64, triangles (F, 3) int64[, colors (V, 3) uint8]) as PointSetVolume.extract_mesh returns them: the
     zero set of the point-set surface of `cloud` (a PointCloud or (n, 3) points) with `normals` (n, 3) on a lattice of step voxel.
     radius: default 3 voxel.  bounds (lo, hi): default the box of the points taking part, padded by the radius.  colors: None =
-    blended when the cloud has them.  simplify_cell, smooth, backend, device: as extract_mesh's and the volume's.
+    blended when the cloud has them.  simplify_cell, smooth, denoise, backend, device: as extract_mesh's and the volume's.
     stats (dict): receives points, bricks, allocated_share, candidates_max, vertices, faces."""
     voxel = float(voxel)
     radius = 3.0 * voxel if radius is None else float(radius)
@@ -293,7 +293,7 @@ def reconstruct(cloud, normals, voxel, radius=None, min_points=4, bounds=None, c
     lo, hi = cloud_bounds(points, normals, radius) if bounds is None else bounds
     vol = PointSetVolume((lo, hi, voxel), radius, min_points=min_points, colors=colors, backend=backend, device=device)
     vol.set_cloud(cloud, normals)
-    mesh = vol.extract_mesh(simplify_cell=simplify_cell, smooth=smooth)
+    mesh = vol.extract_mesh(simplify_cell=simplify_cell, smooth=smooth, denoise=denoise)
     if stats is not None:
         cs = vol.cloud_stats()
         stats.update(points=cs["points"], bricks=cs["bricks"], allocated_share=cs["allocated_share"],
