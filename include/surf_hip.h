@@ -1522,6 +1522,72 @@ int surf_denoise_vertex_step(const float* positions_in, float* positions_out, in
                              const float* records, const int64_t* corner_order, const int64_t* corner_start,
                              const uint8_t* boundary, int pin_boundary, void* stream);
 
+/*
+ * Textured meshes: the source photographs baked into one atlas image (surf_amd/mesh_texture.py, backend="device";
+ * mesh_texture.hip).  Added under SURF_ABI_VERSION 41 without a bump, like the entry points above.  The device path returns the
+ * host path's arrays: both follow the rule below in fp32 with separate multiplies and adds (-ffp-contract=off), one operation per
+ * operator in the written order, and no function beyond + - * / sqrtf floorf fabsf, which round correctly in numpy and on gfx950
+ * (the camera centre alone is formed in float64 by the caller and rounded once).  Positions, faces and vertex order are never
+ * touched.  Dot-like sums are (t0 + t1) + t2.
+ *
+ * THE RULE.  vertices (n,3) fp32, faces (m,3) int32, T = texels_per_edge an integer in [4, 64], K views in order.
+ *   1. atlas layout, arithmetic only.  Faces 2k and 2k+1 share cell k, T+1 texels wide and T tall, at column k % cols and row
+ *      k / cols of the atlas, with ncell = ceil(m / 2), cols = ceil(sqrt(ncell)), rows = ceil(ncell / cols); the atlas is
+ *      (Ha, Wa) = (rows T, cols (T+1)) texels, row 0 first.  Texel (X, Y): i = X % (T+1), j = Y % T, k = (Y / T) cols + X / (T+1).
+ *      Face A = 2k owns the texels with i + j <= T-1, face B = 2k+1 those with i + j >= T.  A's corners 0, 1, 2 sit at the centres
+ *      of texels (i, j) = (0, 0), (T-2, 0), (0, T-2), B's at (T, T-1), (2, T-1), (T, 1): the bilinear footprint of every point of a
+ *      triangle lies in texels of its own face, so there is no dilation pass.  A texel whose face index is >= m belongs to no face.
+ *      uv (3m, 2) fp32, one row per face corner: u = (x + 0.5) / Wa, v = 1 - (y + 0.5) / Ha of the corner's texel (x, y) of the
+ *      atlas, formed in float64 and rounded once (v points up, as an OBJ file has it).
+ *   2. texel to point.  den = (float)(T-2).  A: beta = (float)i / den, gamma = (float)j / den.  B: beta = (float)(T-i) / den,
+ *      gamma = (float)(T-1-j) / den.  The guard texels beyond the hypotenuse keep their extrapolated barycentrics (beta + gamma
+ *      > 1).  With a, b, c the face's corners: e1 = b - a, e2 = c - a, p = (a + beta * e1) + gamma * e2 per axis,
+ *      n = (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z, e1x*e2y - e1y*e2x), nn = (nx*nx + ny*ny) + nz*nz.  The face is NEVER SEEN, and
+ *      no view is looked at, if an index is outside [0, n), a coordinate of a corner is not finite, or nn is not in (0, FLT_MAX].
+ *      Otherwise ln = sqrtf(nn).
+ *   3. one view: P (12) = world -> (x z, y z, z) in pixel indices of its image, image (H, W, 3) fp32 and the mesh's own depth map
+ *      D (H, W) fp32 from that camera (0 = nothing hit), H, W >= 2, centre (3) = -M^-1 t of P = [M | t].
+ *        cx = ((P0*px + P1*py) + P2*pz) + P3, cy with P4..P7, z with P8..P11;  skip unless z > z_min
+ *        x = cx / z, y = cy / z;  skip unless 0 <= x <= W-1 and 0 <= y <= H-1              (float compares: a NaN fails)
+ *        d = centre - p per axis, nd = (nx*dx + ny*dy) + nz*dz, dd = (dx*dx + dy*dy) + dz*dz
+ *        cos = nd / (ln * sqrtf(dd)), cos = fabsf(cos) when two_sided;  skip unless cos >= min_cos
+ *        x0 = min((int)floorf(x), W-2), y0 = min((int)floorf(y), H-2), u = x - (float)x0, v = y - (float)y0    (u = 1 on the
+ *        last column); the four pixels (y0, x0), (y0, x0+1), (y0+1, x0), (y0+1, x0+1) must ALL have D > 0, z <= D + depth_tol and
+ *        D <= z + depth_tol, else skip: silhouettes take colour from neither side.  (The second half keeps a texel of a front
+ *        surface from blending in the pixels beside it that show a surface far behind it.)
+ *        colour per channel = lerp(lerp(c00, c01, u), lerp(c10, c11, u), v) with lerp(a, b, s) = (1 - s) * a + s * b
+ *        w = cos, then w = w * cos power-1 times (power an integer in [1, 16]: no powf)
+ *   4. all views, in the order 0..K-1:  sum_c = sum_c + w * colour_c per channel, sum_w = sum_w + w, count = count + 1, all
+ *      starting from 0.  The accumulators live in memory between launches of at most SURF_FUSE_MAX_VIEWS views, so the result
+ *      does not depend on how the views are cut into launches.
+ *   5. finish.  A texel of no face gets `fill`.  One with sum_w > 0 gets sum_c / sum_w per channel.  Any other texel of a face
+ *      whose indices are inside [0, n) gets, when vertex colours (n,3) uint8 are given, the mix of its corners' colours
+ *      C = (float)colour / 255.0f:  s = beta + gamma;  if s > 1: beta = beta / s, gamma = gamma / s;  alpha = (1 - beta) - gamma;
+ *      value = (alpha * Ca + beta * Cb) + gamma * Cc.  Every texel left gets `fill`.  Then q = value * 256,
+ *      q = fmin(fmax(q, 0), 255), (uint8)q - surf_fuse_vertex_colors' quantisation.
+ *
+ * Entry points, in the order surf_amd.ops.bake_texture calls them.  The depth maps come from surf_raster_first_hit with K = I,
+ * w2c = P, h = Hup = H, w = Wup = W: the upper 32 bits of its keys.
+ *   surf_texture_pack_view: record (H, W, 4) fp32 = (r, g, b, D) per pixel from image (H, W, 3) and depth (H, W): a bilinear tap
+ *     is one 16-byte load that carries colour and depth.
+ *   surf_texture_bake: rules 1-4 for n_views >= 0 views, one texel per lane.  sums (Ha Wa, 4) fp32 = (sum_r, sum_g, sum_b, sum_w),
+ *     count (Ha Wa) int32 or null.  first != 0: the accumulators start from 0 whatever the arrays hold, and every entry is
+ *     written; first == 0: they continue from the arrays.  h_P (n_views,12), h_centre (n_views,3), h_hw (n_views,2) = (H, W) and
+ *     h_records (n_views) device pointers are HOST arrays.  No atomics: a texel has one owner.
+ *   surf_texture_finish: rule 5, atlas (Ha, Wa, 3) uint8; vertex_colors (n,3) uint8 or null.  Every texel is written.
+ * A null pointer, n < 0, m < 1, T outside [4, 64], cols or rows < 1, rows cols < ceil(m / 2), n_views < 0, power outside
+ * [1, 16], H or W < 2 and a depth_tol, min_cos or z_min that is NaN are SURF_E_ARG.  n_views > SURF_FUSE_MAX_VIEWS, n or
+ * m > 2^31 - 1, an atlas of 2^31 texels or more and a view of 2^31 / 4 pixels or more are SURF_E_LIMIT.  All are reported before
+ * any launch; what does not depend on a view's (H, W) or record pointer, before a host array is read.
+ */
+int surf_texture_pack_view(const float* image, const float* depth, int H, int W, float* record, void* stream);
+int surf_texture_bake(const float* vertices, int64_t n, const int32_t* faces, int64_t m, int T, int cols, int rows,
+                      const float* h_P, const float* h_centre, const float* const* h_records, const int* h_hw, int n_views,
+                      float z_min, float depth_tol, float min_cos, int power, int two_sided, int first, float* sums,
+                      int32_t* count, void* stream);
+int surf_texture_finish(const float* sums, int64_t n, const int32_t* faces, int64_t m, int T, int cols, int rows,
+                        const uint8_t* vertex_colors, float fill, uint8_t* atlas, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,7 +27,11 @@ pairs with which offset.  --sweep runs all 3 x 2 x 2 = 12 combinations on ONE lo
 and one evaluation each), prints one line per combination and a final line naming the combination whose Chamfer is closest to
 --reference_chamfer: twelve candidates and a one-command discriminator instead of one guess that may scramble the checkpoint.
 --reference_chamfer X: the reference's own number for this scan (or the published mean 1.05); "delta" = ours - X is then the
-quantity north_star bounds by 0.01."""
+quantity north_star bounds by 0.01.
+--texture [--texture_texels T --texture_depth_tol X --texture_min_cos C --texture_power N --texture_two_sided --texture_backend host]:
+the world-frame mesh that is written also gets a texture atlas baked from ALL photographs of the item at their full resolution
+(surf_amd/mesh_texture.py) -> scan<N>_textured.obj, .mtl and .png beside the PLY, and a `texture` block in the record; the PLY and
+the scores are what they are without it.  The tolerance is in the written mesh's own units, the world frame."""
 import argparse
 import json
 import os
@@ -105,6 +109,17 @@ def parse_args(argv=None):
     ap.add_argument("--deviation_max_dist", type=float, default=None,
                     help="vertices without a face of the other mesh nearer than this count as `beyond` (default: the diagonal of "
                          "the two meshes' joint bounding box)")
+    ap.add_argument("--texture", action="store_true",
+                    help="also bake all photographs of the item into a texture atlas of the mesh that is written "
+                         "(surf_amd/mesh_texture.py) -> scan<N>_textured.obj, .mtl and .png beside the PLY")
+    ap.add_argument("--texture_texels", type=int, default=8, metavar="T", help="texels along a face's edge, 4..64: T (T+1) / 2 a face")
+    ap.add_argument("--texture_depth_tol", type=float, default=None,
+                    help="a texel further than this behind the mesh's own depth map is hidden from that photograph, in the written "
+                         "mesh's own units (the world frame; default: 2 steps of the --mesh_resolution lattice)")
+    ap.add_argument("--texture_min_cos", type=float, default=0.2, help="photographs that see a face more obliquely are not used for it")
+    ap.add_argument("--texture_power", type=int, default=4, metavar="N", help="a photograph's weight is cos^N, 1..16")
+    ap.add_argument("--texture_two_sided", action="store_true", help="photographs of a face's back side count too")
+    ap.add_argument("--texture_backend", default="device", choices=["host", "device"])
     ap.add_argument("--downsample_density", type=float, default=0.2)
     ap.add_argument("--patch_size", type=float, default=60)
     ap.add_argument("--max_dist", type=float, default=20)
@@ -134,9 +149,25 @@ def denoise_params(args):
         raise SystemExit(f"dtu_chamfer: {e}")
 
 
+def texture_params(args, voxel):
+    """The --texture_* flags as mesh_texture's argument dict, or None without --texture (a Namespace built by hand may lack them).
+    voxel: the world-frame step of the extraction lattice, of which the default depth tolerance is two."""
+    if not getattr(args, "texture", False):
+        return None
+    from surf_amd.mesh_texture import check_params
+    tol = getattr(args, "texture_depth_tol", None)
+    try:
+        return check_params({"texels_per_edge": getattr(args, "texture_texels", 8), "depth_tol": 2.0 * voxel if tol is None else tol,
+                             "min_cos": getattr(args, "texture_min_cos", 0.2), "power": getattr(args, "texture_power", 4),
+                             "two_sided": getattr(args, "texture_two_sided", False)})
+    except ValueError as e:
+        raise SystemExit(f"dtu_chamfer: {e}")
+
+
 def run(args, state=None):
     """Returns the JSON record.  state (dict, tests): receives the live `model`, the loader's `item` and the final normalised-frame
-    `vertices` / `triangles` of the (last) evaluation."""
+    `vertices` / `triangles` of the (last) evaluation; with --texture also the world-frame `world_vertices`, `texture_views`, `uv`
+    and `atlas`."""
     from surf_amd import conf as C
     from surf_amd import mesh_io, synthetic
     from surf_amd.datasets import get_loader
@@ -160,6 +191,9 @@ def run(args, state=None):
         except ValueError as e:
             raise SystemExit(f"dtu_chamfer: {e}")
     denoise = denoise_params(args)
+    texture_on = bool(getattr(args, "texture", False))
+    if texture_on:
+        texture_params(args, 1.0)                        # a refused flag ends the run before the model is loaded
     deviation = bool(getattr(args, "deviation", False))
     if deviation and smooth is None and denoise is None and args.simplify_cell is None:
         raise SystemExit("dtu_chamfer: --deviation compares the mesh before and after --denoise_iters / --smooth_iters / "
@@ -262,6 +296,7 @@ def run(args, state=None):
             if normals is not None:
                 normals = mesh_io.transform_normals(normals, scale_mat)
             mesh_io.write_ply(mesh_path, vw, t, normals=normals, colors=colors)
+            written = vw
         else:
             normals, colors = attrs.get("normals"), attrs.get("colors")
             before = (v, t)
@@ -277,9 +312,24 @@ def run(args, state=None):
                 v, t, normals, colors, simplified = simplify_step(v, t, args.simplify_cell, normals, colors, args.simplify_backend, dev)
                 if state is not None:
                     state.update(vertices=v, triangles=t)
-            mesh_io.export_mesh(mesh_path, v, t, item["scale_mat"], normals=normals, colors=colors)   # runner.py:236-240
+            written = mesh_io.export_mesh(mesh_path, v, t, item["scale_mat"], normals=normals, colors=colors)   # runner.py:236-240
         if len(t) == 0:
             raise SystemExit(f"dtu_chamfer: --simplify_cell {args.simplify_cell} leaves no face (the cell swallows the mesh)")
+        textured = None
+        if texture_on:                           # on the world-frame mesh that was written, from every photograph of the item
+            from surf_amd.fusion import similarity_scale
+            from surf_amd.mesh_texture import texture_step, view_from_item
+            world_step = similarity_scale(item["scale_mat"].detach().cpu().numpy().reshape(4, 4)) * 2.0 / (args.mesh_resolution - 1)
+            tviews = [view_from_item(item, k) for k in range(int(item["intrs"].reshape(-1, 4, 4).shape[0]))]
+            try:
+                uv, atlas, textured = texture_step(written, t, tviews, texture_params(args, world_step),
+                                                   backend=getattr(args, "texture_backend", "device"), device=dev,
+                                                   vertex_colors=colors)
+            except ValueError as e:
+                raise SystemExit(f"dtu_chamfer: {e}")
+            textured["files"] = list(mesh_io.write_obj(os.path.splitext(mesh_path)[0] + "_textured.obj", written, t, uv, atlas))
+            if state is not None:
+                state.update(world_vertices=written, texture_views=tviews, uv=uv, atlas=atlas)
         deviated = None
         if deviation:                            # mesh B is the mesh that is written, both in the normalised frame
             from surf_amd.mesh_distance import deviation_step
@@ -303,7 +353,7 @@ def run(args, state=None):
                 "seconds": {"load": t_load, "val_forward": t_val, "clean": t_clean, "evaluate": t_eval,
                             **({} if t_attr is None else {"vertex_attributes": t_attr})},
                 **({} if denoised is None else {"denoise": denoised}), **({} if smoothed is None else {"smooth": smoothed}), **({} if simplified is None else {"simplify": simplified}),
-                **({} if deviated is None else {"deviation": deviated})}
+                **({} if deviated is None else {"deviation": deviated}), **({} if textured is None else {"texture": textured})}
 
     if not args.sweep:
         rec = evaluate()

@@ -54,6 +54,13 @@ units, 0 = no hit), <view>_normal.png and, with --colors, <view>_color.png; the 
 over them, the share of the view's measured pixels the model also hits and the median / 90th percentile of |view depth - model
 depth| over those, in world units and in lattice steps (fusion.view_residual: a quality number that needs no ground truth) - and
 `render_views_ms`.  Without the switch the record and the files are what they were.
+With --texture [--texture_texels T --texture_depth_tol_mm X --texture_min_cos C --texture_power N --texture_two_sided
+--texture_backend host] the mesh that is written - after --clean_mesh, --denoise_iters, --smooth_iters and --simplify_mm - also gets
+a texture atlas baked from the reference photographs of the fused views at their full resolution (surf_amd/mesh_texture.py,
+csrc/mesh_texture.hip: every texel is projected into every photograph and tested against the mesh's own z-buffer there) ->
+<name>_textured.obj, .mtl and .png beside the unchanged PLY; with --colors the vertex colours fill what no photograph sees.  The
+record gains `texture` {texels_per_edge, atlas, faces, texels_owned, texels_seen, seen_share, faces_unseen, views,
+views_per_seen_texel, depth_tol, min_cos, power, files, ms}.  Without the switch the record and the files are what they were.
 Measurement harness like scripts/dtu_chamfer.py: one scan per call, no logging framework, no resume logic."""
 import argparse
 import json
@@ -157,6 +164,17 @@ def parse_args(argv=None):
     ap.add_argument("--deviation_max_mm", type=float, default=None,
                     help="vertices without a face of the other mesh nearer than this count as `beyond` (world units; default: "
                          "the diagonal of the two meshes' joint bounding box)")
+    ap.add_argument("--texture", action="store_true",
+                    help="also bake the fused views' reference photographs into a texture atlas of the mesh that is written "
+                         "(surf_amd/mesh_texture.py) -> <name>_textured.obj, .mtl and .png beside the PLY")
+    ap.add_argument("--texture_texels", type=int, default=8, metavar="T", help="texels along a face's edge, 4..64: T (T+1) / 2 a face")
+    ap.add_argument("--texture_depth_tol_mm", type=float, default=None,
+                    help="a texel further than this behind the mesh's own depth map is hidden from that photograph (world units; "
+                         "DTU: millimetres; default: 2 lattice steps)")
+    ap.add_argument("--texture_min_cos", type=float, default=0.2, help="photographs that see a face more obliquely are not used for it")
+    ap.add_argument("--texture_power", type=int, default=4, metavar="N", help="a photograph's weight is cos^N, 1..16")
+    ap.add_argument("--texture_two_sided", action="store_true", help="photographs of a face's back side count too")
+    ap.add_argument("--texture_backend", default="device", choices=["host", "device"])
     ap.add_argument("--eval_dir", default=None, help="DTU evaluation data (ObsMask/, Points/stl/): also report the Chamfer distance")
     ap.add_argument("--eval_device", default="cpu", choices=["cpu", "gpu"])
     ap.add_argument("--downsample_density", type=float, default=0.2)
@@ -194,6 +212,34 @@ def denoise_params(args):
                              "max_move": getattr(args, "denoise_max_move_mm", None)})
     except ValueError as e:
         raise SystemExit(f"fuse_scene: {e}")
+
+
+def texture_params(args, voxel):
+    """The --texture_* flags as mesh_texture's argument dict, or None without --texture (a Namespace built by hand may lack them).
+    voxel: the lattice step, of which the default depth tolerance is two."""
+    if not getattr(args, "texture", False):
+        return None
+    from surf_amd.mesh_texture import check_params
+    tol = getattr(args, "texture_depth_tol_mm", None)
+    try:
+        return check_params({"texels_per_edge": getattr(args, "texture_texels", 8), "depth_tol": 2.0 * voxel if tol is None else tol,
+                             "min_cos": getattr(args, "texture_min_cos", 0.2), "power": getattr(args, "texture_power", 4),
+                             "two_sided": getattr(args, "texture_two_sided", False)})
+    except ValueError as e:
+        raise SystemExit(f"fuse_scene: {e}")
+
+
+def texture_mesh(v, t, colors, views, params, path, backend, dev):
+    """--texture: bake `views` into an atlas of the mesh (v, t) and write <path>.obj / .mtl / .png: (the `texture` block of the
+    record, uv, atlas)."""
+    from surf_amd import mesh_io
+    from surf_amd.mesh_texture import texture_step
+    try:
+        uv, atlas, rec = texture_step(v, t, views, params, backend=backend, device=dev, vertex_colors=colors)
+    except ValueError as e:
+        raise SystemExit(f"fuse_scene: {e}")
+    rec["files"] = list(mesh_io.write_obj(path, v, t, uv, atlas))
+    return rec, uv, atlas
 
 
 def smooth_params(args):
@@ -308,6 +354,8 @@ def run(args, state=None):
                          "of 2^31 points (and takes 8 to 20 B per point): use --sparse")
     volume = fusion.FusionVolume((lo, hi, voxel), trunc=args.trunc_voxels * voxel, colors=args.colors, device=dev, sparse=args.sparse)
     ms["lattice"] = 1e3 * (time.perf_counter() - t0)
+    texture = texture_params(args, voxel)
+    texture_views = []                                  # --texture: the reference photograph of every fused view, world frame
 
     def sync():
         if dev.type == "cuda":
@@ -333,6 +381,9 @@ def run(args, state=None):
             out = model("val", inputs, cos_anneal_ratio=1.0)
         sync()
         pending.append(fusion.view_from_val(item, out, depth=args.depth))
+        if texture is not None:
+            from surf_amd.mesh_texture import view_from_item
+            texture_views.append(view_from_item(item, 0))
         if args.point_cloud:
             cloud_views.append(pending[-1])
         if render_dir is not None:
@@ -442,8 +493,15 @@ def run(args, state=None):
     mesh_path = os.path.join(args.out_dir, "meshes", "fused", f"{name}.ply")
     mesh_io.write_ply(mesh_path, v, t, colors=colors)
     ms["write"] = 1e3 * (time.perf_counter() - t0)
+    textured = None
+    if texture is not None:                             # on the mesh that is written; the PLY stays what it is
+        textured, uv, atlas = texture_mesh(v, t, colors, texture_views, texture,
+                                           os.path.join(args.out_dir, "meshes", "fused", f"{name}_textured.obj"),
+                                           getattr(args, "texture_backend", "device"), dev)
     if state is not None:
         state.update(model=model, volume=volume, vertices=v, triangles=t, colors=colors)
+        if textured is not None:
+            state.update(texture_views=texture_views, uv=uv, atlas=atlas)
         if cloud is not None:
             state.update(cloud=cloud)
         if cloud_mesh_record is not None:
@@ -487,6 +545,8 @@ def run(args, state=None):
         rec.update(simplify=simplified)
     if deviated is not None:                            # without the flag the record is what it was
         rec.update(deviation=deviated)
+    if textured is not None:                            # without the flag the record is what it was
+        rec.update(texture=textured)
     if model_residual is not None:                      # without the switch the record is what it was
         rec.update(model_residual=model_residual, render_views_ms=render_ms)
     if filtered is not None:

@@ -188,6 +188,84 @@ def read_ply_mesh(path):
     return v, faces["idx"].astype(np.int64)
 
 
+def write_obj(path, vertices, faces, uv, atlas, normals=None):
+    """A textured mesh (mesh_texture.bake_texture) as Wavefront OBJ: <name>.obj (`mtllib`, `v` with 9 significant digits, `vt` one
+    per face corner, optional `vn`, `f a/ta b/tb c/tc` or `a/ta/na ...`, indices from 1), <name>.mtl (one material with `map_Kd`)
+    and <name>.png (the atlas, row 0 at the top: v = 1) side by side.  uv (3m, 2) fp32, atlas (Ha, Wa, 3) uint8, normals (n, 3)
+    fp32 per vertex or None.  Returns the three paths."""
+    from PIL import Image
+    v = np.asarray(vertices, dtype=np.float32).reshape(-1, 3)
+    f = np.asarray(faces).reshape(-1, 3).astype(np.int64)
+    uv = np.asarray(uv, dtype=np.float32).reshape(-1, 2)
+    atlas = np.asarray(atlas)
+    if f.size and (f.min() < 0 or f.max() >= max(len(v), 1)):
+        raise ValueError("triangle index out of range")
+    if len(uv) != 3 * len(f):
+        raise ValueError(f"uv: expected one (u, v) row per face corner, {3 * len(f)} rows, got {len(uv)}")
+    if atlas.dtype != np.uint8 or atlas.ndim != 3 or atlas.shape[2] != 3 or atlas.size == 0:
+        raise ValueError("atlas: expected a uint8 (Ha, Wa, 3) image")
+    if normals is not None:
+        normals = np.asarray(normals, dtype=np.float32)
+        if normals.shape != v.shape:
+            raise ValueError("normals: expected one (x, y, z) row per vertex")
+    stem = os.path.splitext(os.path.abspath(path))[0]
+    name = os.path.basename(stem)
+    os.makedirs(os.path.dirname(stem), exist_ok=True)
+    Image.fromarray(atlas).save(stem + ".png")
+    with open(stem + ".mtl", "w") as out:
+        out.write(f"# surf_amd mesh export\nnewmtl {name}\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {name}.png\n")
+    corner = np.arange(1, 3 * len(f) + 1, dtype=np.int64).reshape(-1, 3)
+    with open(stem + ".obj", "w") as out:
+        out.write(f"# surf_amd mesh export\nmtllib {name}.mtl\nusemtl {name}\n")
+        out.write("".join(f"v {x:.9g} {y:.9g} {z:.9g}\n" for x, y, z in v.tolist()))
+        out.write("".join(f"vt {a:.9g} {b:.9g}\n" for a, b in uv.tolist()))
+        if normals is None:
+            out.write("".join(f"f {a}/{ta} {b}/{tb} {c}/{tc}\n" for (a, b, c), (ta, tb, tc) in zip((f + 1).tolist(), corner.tolist())))
+        else:
+            out.write("".join(f"vn {x:.9g} {y:.9g} {z:.9g}\n" for x, y, z in normals.tolist()))
+            out.write("".join(f"f {a}/{ta}/{a} {b}/{tb}/{b} {c}/{tc}/{c}\n"
+                              for (a, b, c), (ta, tb, tc) in zip((f + 1).tolist(), corner.tolist())))
+    return stem + ".obj", stem + ".mtl", stem + ".png"
+
+
+def read_obj(path):
+    """Reads back what write_obj wrote: {"vertices" (n, 3) fp32, "faces" (m, 3) int32, "uv" (3m, 2) fp32 in face-corner order,
+    "normals" (n, 3) fp32 or None, "atlas" (Ha, Wa, 3) uint8 or None (the `map_Kd` image of the `mtllib`, found beside the file)}.
+    9 significant digits return every fp32 to the bit."""
+    v, vt, vn, fv, ft, mtl = [], [], [], [], [], None
+    with open(path) as src:
+        for line in src:
+            w = line.split()
+            if not w or w[0].startswith("#"):
+                continue
+            if w[0] == "v":
+                v.append(w[1:4])
+            elif w[0] == "vt":
+                vt.append(w[1:3])
+            elif w[0] == "vn":
+                vn.append(w[1:4])
+            elif w[0] == "mtllib":
+                mtl = w[1]
+            elif w[0] == "f":
+                if len(w) != 4:
+                    raise ValueError("not a triangle mesh")
+                parts = [c.split("/") for c in w[1:]]
+                fv.append([int(p[0]) - 1 for p in parts])
+                ft.append([int(p[1]) - 1 for p in parts])
+    vt = np.array(vt, dtype=np.float64).reshape(-1, 2).astype(np.float32)
+    atlas = None
+    if mtl is not None:
+        here = os.path.dirname(os.path.abspath(path))
+        with open(os.path.join(here, mtl)) as src:
+            maps = [l.split()[1] for l in src if l.split()[:1] == ["map_Kd"]]
+        if maps:
+            from PIL import Image
+            atlas = np.asarray(Image.open(os.path.join(here, maps[0])).convert("RGB"))
+    return {"vertices": np.array(v, dtype=np.float64).reshape(-1, 3).astype(np.float32),
+            "faces": np.array(fv, dtype=np.int32).reshape(-1, 3), "uv": vt[np.array(ft, dtype=np.int64).reshape(-1)],
+            "normals": np.array(vn, dtype=np.float64).reshape(-1, 3).astype(np.float32) if vn else None, "atlas": atlas}
+
+
 def export_mesh(path, vertices, triangles, scale_mat=None, normals=None, colors=None):
     """runner.py:231-240: optional scale_mat transform, then PLY export.  Returns the transformed vertices.  normals / colors
     (per vertex, optional): written as nx ny nz / red green blue; normals go through scale_mat's linear part (transform_normals:

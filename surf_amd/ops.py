@@ -6,6 +6,7 @@ the library) and 4x4 camera inversions.
 """
 import ctypes
 import os
+import time
 
 import numpy as np
 import torch
@@ -1309,6 +1310,24 @@ def raster_first_hit(vertices, faces, intr, c2w, hw, upscale=1):
     return torch.where(zbuf == -1, torch.full_like(zbuf, -1), zbuf & 0xffffffff)
 
 
+def raster_depth(vertices, faces, P, hw):
+    """The z-buffer of a mesh from the camera P (3, 4) fp32 on the host (world -> (x z, y z, z) in pixel indices): (H, W) fp32,
+    the depth of the nearest face at every pixel, 0 where nothing is hit.  surf_raster_first_hit in P's own pixel units (K = I,
+    w2c = P, one sample per pixel): the depth raster_first_hit throws away, the upper 32 bits of the keys.  No faces: all 0."""
+    _chk(vertices, torch.float32, "vertices")
+    _chk(faces, torch.int32, "faces")
+    H, W = int(hw[0]), int(hw[1])
+    if faces.shape[0] == 0:
+        return torch.zeros((H, W), dtype=torch.float32, device=vertices.device)
+    K = np.eye(3, dtype=np.float32)
+    w2c = np.ascontiguousarray(P, dtype=np.float32).reshape(3, 4)
+    zbuf = torch.full((H, W), -1, dtype=torch.int64, device=vertices.device)          # all ones = empty
+    _lib.lib().surf_raster_first_hit(_p(vertices), _p(faces), faces.shape[0], _np_ptr(K), _np_ptr(w2c), H, W, H, W, _p(zbuf),
+                                     _stream())
+    depth = (zbuf >> 32).to(torch.int32).view(torch.float32)
+    return torch.where(zbuf == -1, torch.zeros_like(depth), depth)
+
+
 # ------------------------------------------------------------------------------------------------
 # DTU Chamfer evaluation (dtu_eval.hip): mesh sampling, greedy thinning, capped nearest neighbour, all fp64
 # ------------------------------------------------------------------------------------------------
@@ -2127,7 +2146,77 @@ def denoise_mesh(vertices, faces, normal_iterations=10, vertex_iterations=10, si
 # mesh deviation (mesh_distance.hip): exact point-to-triangle distances; the rule is in include/surf_hip.h
 # ------------------------------------------------------------------------------------------------
 
-MESHDIST_HOST_READS = 2          # the LEAST point_to_mesh waits for the device: one more per growth of the cell, see its docstring
+def texture_pack_view(image, depth):
+    """surf_texture_pack_view: image (H, W, 3) and depth (H, W) fp32 -> the (H, W, 4) records (r, g, b, D) surf_texture_bake taps."""
+    _chk(image, torch.float32, "image")
+    _chk(depth, torch.float32, "depth")
+    H, W = (int(s) for s in depth.shape)
+    if depth.dim() != 2 or tuple(image.shape) != (H, W, 3):
+        raise ValueError(f"texture_pack_view: image (H, W, 3) and depth (H, W), got {tuple(image.shape)} and {tuple(depth.shape)}")
+    record = torch.empty((H, W, 4), dtype=torch.float32, device=image.device)
+    _lib.lib().surf_texture_pack_view(_p(image), _p(depth), H, W, _p(record), _stream())
+    return record
+
+
+def bake_texture(vertices, faces, views, T, cols, rows, depth_tol, min_cos=0.2, power=4, two_sided=False, z_min=0.0, fill=0.5,
+                 vertex_colors=None, count=False, chunk=None, stages=None):
+    """The device path of mesh_texture.bake_texture (the rule: include/surf_hip.h above surf_texture_*): vertices (n, 3) fp32,
+    faces (m >= 1, 3) int32 and vertex_colors (n, 3) uint8 or None on the device; views: (P (12,) fp32 and centre (3,) fp32 on the
+    host, image (H, W, 3) and mesh depth (H, W) fp32 on the device) in order; (cols, rows): mesh_texture.atlas_layout's.  The
+    views go `chunk` (<= FUSE_MAX_VIEWS) to a launch; their packed records live only for their launch, and the accumulators stay
+    in memory between launches.  Returns (atlas (Ha, Wa, 3) uint8, sums (Ha, Wa, 4) fp32, count (Ha, Wa) int32 or None).  No
+    host read.  stages: a list that receives (name, ms) per stage, each after a device synchronisation."""
+    _chk(vertices, torch.float32, "vertices")
+    _chk(faces, torch.int32, "faces")
+    dev = vertices.device
+    n, m = int(vertices.shape[0]), int(faces.shape[0])
+    if vertex_colors is not None:
+        _chk(vertex_colors, torch.uint8, "vertex_colors")
+        if tuple(vertex_colors.shape) != (n, 3):
+            raise ValueError(f"bake_texture: vertex_colors ({n}, 3)")
+    chunk = FUSE_MAX_VIEWS if chunk is None else chunk
+    if not 1 <= int(chunk) <= FUSE_MAX_VIEWS:
+        raise ValueError(f"bake_texture: chunk must be in [1, {FUSE_MAX_VIEWS}], got {chunk!r}")
+    Ha, Wa = int(rows) * int(T), int(cols) * (int(T) + 1)
+    vbuf = vertices if n else torch.zeros((1, 3), dtype=torch.float32, device=dev)       # n = 0: no face is read, no null pointer
+    sums = torch.empty((Ha, Wa, 4), dtype=torch.float32, device=dev)                     # the first launch writes every entry
+    cnt = torch.empty((Ha, Wa), dtype=torch.int32, device=dev) if count else None
+    atlas = torch.empty((Ha, Wa, 3), dtype=torch.uint8, device=dev)
+    L = _lib.lib()
+    t_stage = [time.perf_counter()]
+    totals = {}
+
+    def stage(name):
+        if stages is not None:
+            torch.cuda.synchronize(dev)
+            now = time.perf_counter()
+            totals[name] = totals.get(name, 0.0) + 1e3 * (now - t_stage[0])
+            t_stage[0] = now
+
+    for s in range(0, max(len(views), 1), int(chunk)):
+        part = views[s:s + int(chunk)]
+        k = len(part)
+        P = np.ascontiguousarray([np.asarray(v[0], np.float32).reshape(12) for v in part], dtype=np.float32).reshape(k, 12)
+        centre = np.ascontiguousarray([np.asarray(v[1], np.float32).reshape(3) for v in part], dtype=np.float32).reshape(k, 3)
+        hw = np.ascontiguousarray([tuple(v[3].shape) for v in part], dtype=np.int32).reshape(k, 2)
+        stage("other")
+        records = [texture_pack_view(v[2], v[3]) for v in part]
+        stage("pack")
+        L.surf_texture_bake(_p(vbuf), n, _p(faces), m, int(T), int(cols), int(rows), _np_ptr(P), _np_ptr(centre),
+                            _ptr_array(records) if k else None, _np_ptr(hw), k, ctypes.c_float(float(z_min)),
+                            ctypes.c_float(float(depth_tol)), ctypes.c_float(float(min_cos)), int(power), int(bool(two_sided)),
+                            int(s == 0), _p(sums), _p(cnt), _stream())
+        stage("bake")
+        del records
+    L.surf_texture_finish(_p(sums), n, _p(faces), m, int(T), int(cols), int(rows), _p(vertex_colors), ctypes.c_float(float(fill)),
+                          _p(atlas), _stream())
+    stage("finish")
+    if stages is not None:
+        stages.extend((k, totals[k]) for k in ("pack", "bake", "finish") if k in totals)
+    return atlas, sums, cnt
+
+
+MESHDIST_HOST_READS = 2         # the LEAST point_to_mesh waits for the device: one more per growth of the cell, see its docstring
 MESHDIST_MAX_AXIS_CELLS = 4096   # SURF_MESHDIST_MAX_AXIS_CELLS of include/surf_hip.h
 MESHDIST_MAX_CELLS = 1 << 26     # SURF_MESHDIST_MAX_CELLS
 MESHDIST_PAIRS_PER_FACE = 8      # SURF_MESHDIST_PAIRS_PER_FACE
